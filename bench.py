@@ -22,8 +22,12 @@ The JSON line also carries:
   roofline      k_sync_diff algorithmic bytes (the key bytes the engine counts per streamed payload: 2 B or 8 B x N,
                 swim_counters.diff_key_bytes) / its HIP-event time, against 8 TB/s; traffic = measured HBM bytes per
                 launch from a committed rocprofv3 PMC summary when available (profiles/), else null.
-  cpu_baseline  the CPU oracle (oracle/swimref.cpp, a port) on a bounded sample: same workload shape at 10k members,
-                timed here on the host on all its cores (worker threads over observer ranges, at most 16) and on one.
+  cpu_baseline  with --full only (null otherwise): the CPU oracle (oracle/swimref.cpp, a port) on a bounded sample:
+                same workload shape at 10k members, timed here on the host on all its cores (worker threads over
+                observer ranges, at most 16) and on one.
+
+A plain run sets up, warms up, times --steps periods, writes its outputs if --dump-outputs DIR is given, and prints the
+line; --full adds the cpu_baseline leg after it (over a minute at the headline size).
 """
 import argparse
 import json
@@ -52,7 +56,13 @@ def parse():
     p.add_argument("--updates", type=int, default=1, help="c3dyn: updateIncarnation calls per period")
     p.add_argument("--members", type=int, default=None, help="default: 100k (c3, c5), 10k (c2)")
     p.add_argument("--loss", type=int, default=None, help="default: 5 (c2), 0 otherwise")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also time the CPU oracle on the same workload shape (cpu_baseline); "
+                        "a plain run only sets up, warms up, times --steps periods and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step left (state hashes, counters, sampled membership rows) as "
+                        "DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without its cpu_baseline leg")
     p.add_argument("--cpu-members", type=int, default=None, help="default: the workload's size if host RAM allows")
     p.add_argument("--cpu-periods", type=int, default=120)
     p.add_argument("--transport", choices=["rccl", "host"], default="rccl", help="N>1 shard exchange")
@@ -167,6 +177,34 @@ def cpu_baseline(a, members, periods):
                       f"{note}"}
 
 
+DUMP_COUNTERS = ("tick", "record_compares", "row_writes", "messages", "gossip_messages", "events", "messages_lost",
+                 "gossips_created", "sync_merges")
+DUMP_ROWS = 8  # sampled observers: 8 rows x 100k records x (2 x 8 B + 2 x 4 B) = 19 MB beside 10 MB of hashes
+
+
+def dump_outputs(c, n, out_dir):
+    """What a caller holds after the last timed step, as float arrays that carry every integer exactly: every
+    observer's state hash (row, fd list, gossip list, events, held gossips, misc) as 32-bit halves, the handle's
+    deterministic counters, and the membership rows of a fixed seeded sample of this rank's observers split into
+    their fields. (The full tables are N x N records: 80 GB at 100k members.)"""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    h = c.state_hash()
+    halves = np.stack([h >> np.uint64(32), h & np.uint64(0xFFFFFFFF)], axis=-1).reshape(h.shape[0], -1)
+    np.save(out / "state_hash.npy", halves.astype(np.float64))
+    ctr = c.counters()
+    np.save(out / "counters.npy", np.array([ctr[k] for k in DUMP_COUNTERS], dtype=np.float64))
+    lo, hi = getattr(c, "lo", 0), getattr(c, "hi", n)
+    obs = np.sort(np.random.default_rng(0x5EED).choice(hi - lo, size=min(DUMP_ROWS, hi - lo), replace=False)) + lo
+    rows = np.stack([c.row(int(o)) for o in obs])  # record = inc | status << 32 | has_metadata << 34 | deadline << 35
+    np.save(out / "row_observers.npy", obs.astype(np.float64))
+    np.save(out / "row_incarnation.npy", (rows & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(out / "row_status.npy", ((rows >> np.uint64(32)) & np.uint64(3)).astype(np.float32))
+    np.save(out / "row_has_metadata.npy", ((rows >> np.uint64(34)) & np.uint64(1)).astype(np.float32))
+    np.save(out / "row_suspicion_deadline.npy", (rows >> np.uint64(35)).astype(np.float64))
+
+
 def workload_name(a, n):
     if a.workload == "c3dyn":
         return (f"C3 with membership evolution: {n} members, full views, preconverged, {a.updates} "
@@ -257,6 +295,8 @@ def main():
         dt = float(t.item())
     ctr = c.counters()
     d = {k: ctr[k] - base[k] for k in ctr}
+    if a.dump_outputs and rank == 0:
+        dump_outputs(c, a.members, a.dump_outputs)
 
     if rank == 0:
         n = a.members
@@ -341,7 +381,7 @@ def main():
         if a.rehearse_shard > 1:
             line["metric"] = "member·periods/sec of ONE slot shard, C5 rehearsal (not the headline)"
             line["config"]["parallelism"] = f"slot shard 0 of {a.rehearse_shard} (peers simulated)"
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             c.close()  # the engine's host buffers go before the oracle's tables
             c = None
             cm, cp = {"c3": (a.cpu_members, a.cpu_periods), "c3dyn": (a.cpu_members, a.cpu_periods),
