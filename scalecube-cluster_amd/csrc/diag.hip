@@ -1,0 +1,184 @@
+// diag.hip — what swim_step prints and measures besides stepping: the SWIM_STATS dump of a gossip tick, the SWIM_EXP
+// dumps after a step (tools/ parse some of these lines), and the SWIM_FLAG_PROFILE event bookkeeping.
+#include "handle.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+
+using namespace swim;
+
+namespace swim {
+
+// SWIM_STATS: the gossip plane's work of tick k (it has just been launched)
+int stats_dump(swim_handle* h, uint32_t k) {
+  const Dev& d = h->d;
+  uint32_t v[8];
+  HIPCK(hipStreamSynchronize(h->stream));
+  const uint32_t* src[8] = {d.rc_n, d.ntl, d.nagroup, d.rp_n, d.slow_n, d.ncfl, d.nrx, d.nrwl};
+  for (int q = 0; q < 8; ++q) HIPCK(hipMemcpy(&v[q], src[q], 4, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> rc(d.N), nf(d.N);
+  HIPCK(hipMemcpy(rc.data(), d.rc_cnt, 4ull * d.N, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy2D(nf.data(), 4, &d.ms[0].nfetch, sizeof(MS), 4, d.N, hipMemcpyDeviceToHost));
+  std::sort(rc.begin(), rc.end());
+  std::sort(nf.begin(), nf.end());
+  // first receipts per target with senders this tick (rtail - rt0), and senders per target
+  std::vector<uint32_t> tl(v[1]), r0(d.N), r1(d.N), tc(d.N), fr, sn;
+  HIPCK(hipMemcpy(tl.data(), d.tlist, 4ull * v[1], hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(r0.data(), d.rt0, 4ull * d.N, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(r1.data(), d.rtail, 4ull * d.N, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(tc.data(), d.tin_off, 4ull * d.N, hipMemcpyDeviceToHost));  // (tin_cnt is reset by then)
+  uint64_t tot = 0;
+  for (uint32_t t : tl) {
+    fr.push_back(r1[t] - r0[t]);
+    if (t + 1 < d.N) sn.push_back(tc[t + 1] - tc[t]);
+    tot += r1[t] - r0[t];
+  }
+  std::sort(fr.begin(), fr.end());
+  std::sort(sn.begin(), sn.end());
+  const size_t nt = fr.size();
+  fprintf(stderr, "stats tick %u: routed %u targets %u groups %u replay %u slow %u contacts %u rx %u rounds %u; "
+          "receipts per member median %u p99 %u max %u; pending fetches median %u p99 %u max %u; "
+          "first receipts %llu, per target median %u p90 %u p99 %u max %u; senders per target median %u max %u\n",
+          k, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], rc[d.N / 2], rc[d.N * 99 / 100], rc[d.N - 1],
+          nf[d.N / 2], nf[d.N * 99 / 100], nf[d.N - 1], (unsigned long long)tot, nt ? fr[nt / 2] : 0,
+          nt ? fr[nt * 9 / 10] : 0, nt ? fr[nt * 99 / 100] : 0, nt ? fr[nt - 1] : 0, sn.empty() ? 0 : sn[sn.size() / 2],
+          sn.empty() ? 0 : sn.back());
+  return SWIM_OK;
+}
+
+// SWIM_EXP & (16 | 128): member-kernel shader cycles per phase since the last step (16: sum over members, 128: max)
+int exp_dump_member_cycles(swim_handle* h) {
+  const Dev& d = h->d;
+  unsigned long long c[5];
+  HIPCK(hipMemcpy(c, d.ctr + 8, sizeof(c), hipMemcpyDeviceToHost));
+  HIPCK(hipMemset(d.ctr + 8, 0, sizeof(c)));
+  fprintf(stderr, "exp: member cycles P0+P1 %llu P2+P3 %llu P4 %llu P5 %llu P6 %llu\n", c[0], c[1], c[2], c[3], c[4]);
+  if (d.exp & 128) {
+    unsigned long long w[2];
+    HIPCK(hipMemcpy(w, d.ctr + 14, sizeof(w), hipMemcpyDeviceToHost));
+    HIPCK(hipMemset(d.ctr + 14, 0, sizeof(w)));
+    fprintf(stderr, "exp: SYNC full walks %llu, largest candidate count %llu\n", w[0], w[1]);
+  }
+  return SWIM_OK;
+}
+
+// SWIM_EXP & 512: per-wave wall clock of the latest member kernel
+int exp_dump_wave_clock(swim_handle* h) {
+  const Dev& d = h->d;
+  const size_t nw = (size_t)(d.NL + 255) / 256 * 4;
+  std::vector<unsigned long long> w16(nw * 16), w(nw * 4);
+  HIPCK(hipMemcpy(w16.data(), d.wt, w16.size() * 8, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < nw; ++i)
+    for (int j = 0; j < 4; ++j) w[4 * i + j] = w16[16 * i + j];
+  const unsigned long long M = (1ull << 48) - 1;
+  unsigned long long t0 = ~0ull, tend = 0;
+  for (size_t i = 0; i < nw; ++i) t0 = std::min(t0, w[4 * i]), tend = std::max(tend, w[4 * i + 3]);
+  std::vector<size_t> ord(nw);
+  for (size_t i = 0; i < nw; ++i) ord[i] = i;
+  // the waves whose bodies end last (a block's waves also wait for each other at the deferred copy-on-write)
+  std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return w[4 * a + 2] > w[4 * b + 2]; });
+  double sst = 0, str = 0, sbd = 0, scw = 0;
+  for (size_t i = 0; i < nw; ++i) {
+    sst += (double)(w[4 * i] - t0), str += (double)((w[4 * i + 1] & M) - w[4 * i]);
+    sbd += (double)(w[4 * i + 2] - (w[4 * i + 1] & M)), scw += (double)(w[4 * i + 3] - w[4 * i + 2]);
+  }
+  fprintf(stderr, "exp512: span %.2f us; mean per wave (us): start %.2f triage %.2f body %.2f cow %.2f\n",
+          (tend - t0) / 100.0, sst / nw / 100.0, str / nw / 100.0, sbd / nw / 100.0, scw / nw / 100.0);
+  for (size_t r = 0; r < 8 && r < nw; ++r) {
+    const size_t i = ord[r];
+    if (r == 0) {  // when the waves of each class finish their bodies (us from the kernel's first wave): quartiles
+      for (int c = 0; c < 4; ++c) {
+        std::vector<double> e;
+        for (size_t j = 0; j < nw; ++j)
+          if ((w[4 * j + 1] >> 56) == (1ull << c)) e.push_back((w[4 * j + 2] - t0) / 100.0);
+        std::sort(e.begin(), e.end());
+        if (!e.empty())
+          fprintf(stderr, "exp512: class %d waves %zu body end min %.1f q1 %.1f med %.1f q3 %.1f max %.1f\n", c, e.size(),
+                  e[0], e[e.size() / 4], e[e.size() / 2], e[3 * e.size() / 4], e.back());
+      }
+    }
+    fprintf(stderr, "exp512: wave %zu start %.2f triage %.2f body %.2f cow %.2f classes %llx busy %llu\n", i,
+            (w[4 * i] - t0) / 100.0, ((w[4 * i + 1] & M) - w[4 * i]) / 100.0, (w[4 * i + 2] - (w[4 * i + 1] & M)) / 100.0,
+            (w[4 * i + 3] - w[4 * i + 2]) / 100.0, w[4 * i + 1] >> 56, (w[4 * i + 1] >> 48) & 255);
+    if (w[4 * i + 1] >> 56) {  // its lead lane's laps in time order, "slot:us since the previous lap"
+      // (slots 0-4: after P0+P1, P2+P3, P4, P5, P6; 5-11: finer laps inside them)
+      unsigned long long prev = w[4 * i + 1] & M;
+      std::vector<std::pair<unsigned long long, int>> laps;
+      for (int j = 0; j < 12; ++j)
+        if (w16[16 * i + 4 + j] >= prev && w16[16 * i + 4 + j] <= w[4 * i + 2]) laps.push_back({w16[16 * i + 4 + j], j});
+      std::sort(laps.begin(), laps.end());
+      fprintf(stderr, "exp512:   laps");
+      for (const auto& l : laps)
+        fprintf(stderr, " %d:%.2f@%.1f", l.second, (l.first - prev) / 100.0, (l.first - t0) / 100.0), prev = l.first;
+      fprintf(stderr, "\n");
+    }
+  }
+  return SWIM_OK;
+}
+
+// SWIM_EXP & 4: gossip-send work counters since the last step
+int exp_dump_gossip_work(swim_handle* h) {
+  const Dev& d = h->d;
+  unsigned long long c[5], u[2];
+  HIPCK(hipMemcpy(c, d.ctr + 8, sizeof(c), hipMemcpyDeviceToHost));
+  HIPCK(hipMemset(d.ctr + 8, 0, sizeof(c)));
+  HIPCK(hipMemcpy(u, d.ctr + C_XU, sizeof(u), hipMemcpyDeviceToHost));
+  HIPCK(hipMemset(d.ctr + C_XU, 0, sizeof(u)));
+  fprintf(stderr, "exp: items %llu contact-bits %llu replayed %llu candidates %llu blocked %llu target-group items %llu "
+          "sender words %llu\n", c[0], c[1], c[2], c[3], c[4], u[0], u[1]);
+  return SWIM_OK;
+}
+
+// W == 1 with SWIM_FLAG_PROFILE: every DIFF_SAMPLE-th tick's k_sync_diff is bracketed by events (the roofline's
+// sample); SWIM_DIFF_SAMPLE overrides it (measurements of the sampling's own cost)
+static uint64_t diff_sample() {
+  static const uint64_t v = [] {
+    const char* e = getenv("SWIM_DIFF_SAMPLE");
+    const unsigned long x = e ? strtoul(e, nullptr, 0) : 0ul;
+    return x >= 1 && x <= 1000 ? (uint64_t)x : (uint64_t)10;
+  }();
+  return v;
+}
+
+// SWIM_FLAG_PROFILE: is this tick's k_sync_diff bracketed by events? On one GPU only every diff_sample()-th (an event
+// pair costs GPU time of its own); the timed launches count their own messages (diff_msgs)
+bool prof_timed(const swim_handle* h, uint64_t tick) {
+  const uint32_t fl = h->cfg.flags;
+  return (fl & (SWIM_FLAG_PROFILE | SWIM_FLAG_PROFILE_ALL)) != 0 &&
+         ((fl & SWIM_FLAG_PROFILE_ALL) || h->d.W > 1 || tick % diff_sample() == 0);
+}
+
+// one event set per tick of a swim_step of n ticks
+int prof_prepare(swim_handle* h, uint32_t n) {
+  if (!(h->cfg.flags & (SWIM_FLAG_PROFILE | SWIM_FLAG_PROFILE_ALL))) return SWIM_OK;
+  while (h->prof.size() < n) {
+    TickEvents te;
+    te.all = (h->cfg.flags & SWIM_FLAG_PROFILE_ALL) ? 1 : 0;
+    for (auto& e : te.ev) HIPCK(hipEventCreate((hipEvent_t*)&e));
+    h->prof.push_back(te);
+  }
+  return SWIM_OK;
+}
+
+// after the step (the stream is idle): the timed kernels' event times into prof_ms
+int prof_accumulate(swim_handle* h, uint64_t first, uint32_t n) {
+  if (!(h->cfg.flags & (SWIM_FLAG_PROFILE | SWIM_FLAG_PROFILE_ALL))) return SWIM_OK;
+  for (uint32_t i = 0; i < n; ++i) {
+    float ms = 0;
+    if (!prof_timed(h, first + i)) continue;
+    if (first + i > 0) {
+      HIPCK(hipEventElapsedTime(&ms, (hipEvent_t)h->prof[i].ev[0], (hipEvent_t)h->prof[i].ev[1]));
+      h->prof_ms[0] += ms;
+      h->prof_diff_launches++;
+    }
+    if (!h->prof[i].all) continue;
+    HIPCK(hipEventElapsedTime(&ms, (hipEvent_t)h->prof[i].ev[2], (hipEvent_t)h->prof[i].ev[3]));
+    h->prof_ms[1] += ms;
+    HIPCK(hipEventElapsedTime(&ms, (hipEvent_t)h->prof[i].ev[4], (hipEvent_t)h->prof[i].ev[5]));
+    h->prof_ms[2] += ms;
+  }
+  return SWIM_OK;
+}
+
+}  // namespace swim

@@ -1,0 +1,150 @@
+// handle.h — private to libswimhip's host side: the handle behind include/swimhip.h and what its source files share.
+//   create.hip    swim_config + environment -> Dev, the allocation table, initialisation
+//   grow.hip      capacity growth between ticks
+//   exchange.hip  the shard exchanges and their transports
+//   step.hip      swim_step: the four tick paths
+//   diag.hip      SWIM_STATS / SWIM_EXP dumps, profile events
+//   group.hip     swim_config.n_gpus > 1: one handle over several shard handles
+//   api.hip       the other extern "C" entry points: fault injection, readback
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <string>
+#include <vector>
+
+#include <rccl/rccl.h>
+
+#include "../../include/swimhip.h"
+#include "../../include/swimhip_shard.h"
+#include "dev_alloc.h"
+#include "engine.h"
+
+struct Group;  // group.hip
+
+struct swim_handle {
+  swim_config cfg;
+  swim::Dev d;
+  hipStream_t stream = nullptr;
+  uint64_t tick = 0;
+  std::string err;
+  swim::DevAllocs mem;  // every device allocation; mem.bytes is swim_counters.device_bytes
+  std::vector<swim_event> host_events;
+  // settings-epoch ring mirrored on the host
+  uint32_t ep_from[swim::MAX_EPOCHS], ep_loss[swim::MAX_EPOCHS], ep_part[swim::MAX_EPOCHS], ep_delay[swim::MAX_EPOCHS];
+  int cur_ep = 0;
+  uint32_t loss = 0;
+  uint32_t delay_idx = 0;                 // default mean delay (index into delays)
+  std::vector<uint32_t> delays{0};        // mean delay ms of each delay index (0: none)
+  bool partitioned = false;
+  std::vector<uint32_t> group;
+  // per-link NetworkEmulator settings: current custom settings and each link's change history (mirrored to HBM)
+  std::map<uint64_t, uint32_t> link_cur;
+  std::map<uint64_t, std::vector<std::pair<uint32_t, uint32_t>>> link_hist;
+  std::vector<swim::TickEvents> prof;  // SWIM_FLAG_PROFILE: one event set per tick of the current swim_step
+  double prof_ms[3] = {0, 0, 0};  // accumulated k_sync_diff, k_member_tick, k_gossip_send
+  uint64_t prof_diff_launches = 0;
+  // row sharding (swimhip_shard.h)
+  swim_shard_spec spec{};
+  ncclComm_t comm = nullptr;
+  unsigned long long* hcnt = nullptr;  // pinned [2W]: send then receive byte counts of the current exchange
+  std::vector<uint8_t> hsend, hrecv;  // SWIM_TRANSPORT_HOST staging
+  double xchg_ms = 0;                 // host time spent in the exchanges
+  bool xflag = false;                 // last exchange: some shard has a gossip slot in use
+  std::vector<uint8_t> joined;  // swim_join: dormant members that were started
+  std::vector<uint32_t> md_cols;  // swim_update_metadata: members that own a metadata-version column
+  std::vector<uint64_t> ugq;  // swim_spread_gossip queue: (member, payload) pairs for P0 of the next tick
+  uint64_t* ug_dev = nullptr;  // device copy of ugq
+  size_t ug_cap = 0;
+  volatile uint32_t* hflag = nullptr; // host-mapped flag word written by k_tick_flag (W == 1)
+  unsigned long long* xi_host_h = nullptr;  // host side of Dev::xi_host
+  hipEvent_t ev_member = nullptr;
+  uint64_t next_scrub = swim::SCRUB;  // tick of the next k_s_scrub (16-bit holder entries, engine.h)
+  bool no_skip = getenv("SWIM_NO_GOSSIP_SKIP") != nullptr;  // debugging aid: always run the gossip data plane
+  bool no_pipe = getenv("SWIM_NO_PIPELINE") != nullptr;    // debugging aid: no early SYNC diff of the next tick
+  bool no_spec = getenv("SWIM_NO_SPECULATION") != nullptr;  // debugging aid: a host wait after every member kernel
+  bool gossip_idle = false;  // W == 1: no gossip slot was in use after the latest member kernel
+  bool gossip_ran = false;   // W == 1: the latest tick ran the gossip plane (the next P4 may have routed receipts)
+  uint64_t growths = 0;      // capacity growth steps so far (grow_caps)
+  uint64_t grow_next = 0;    // grow_caps: no attempt before this tick (the last one found no room)
+  bool rx_pinned = false;    // SWIM_CAPS rx= at create: slot growth keeps Dev::CRCAP
+  // timing aid (bench.py --rehearse-shard): a slot shard alone, its peers' gossip-count deltas taken as zero without
+  // any exchange (not the W-shard simulation's results)
+  bool lone = getenv("SWIM_LONE_SHARD") != nullptr;
+  // timing aid (SWIM_STATS): the gossip plane's work per tick on stderr (routed receipts, targets, active groups,
+  // replay / slow-path sends, contact pairs, RX rows); one stream wait per tick
+  bool stats = getenv("SWIM_STATS") != nullptr;
+  Group* grp = nullptr;  // n_gpus > 1: every call is forwarded to the shards (d holds shard 0's constants only)
+};
+
+#define HIPCK(expr)                                                        \
+  do {                                                                     \
+    hipError_t e_ = (expr);                                                \
+    if (e_ != hipSuccess) {                                                \
+      h->err = std::string(#expr " -> ") + hipGetErrorString(e_);          \
+      return SWIM_EDEVICE;                                                 \
+    }                                                                      \
+  } while (0)
+
+namespace swim {
+#pragma GCC visibility push(hidden)
+
+// a failed DevAllocs::alloc / Staged::add as the handle's error
+inline int alloc_failed(swim_handle* h) {
+  h->err = h->mem.err;
+  return SWIM_ENOMEM;
+}
+
+// `count` elements (at least one) of device memory, registered with the handle
+template <class T>
+int dalloc(swim_handle* h, T** p, size_t count) {
+  *p = (T*)h->mem.alloc((count ? count : 1) * sizeof(T));
+  return *p ? SWIM_OK : alloc_failed(h);
+}
+inline void dfree(swim_handle* h, void* p) { h->mem.free(p); }
+
+inline int fail(swim_handle* h, int rc, const std::string& what) {
+  h->err = what;
+  return rc;
+}
+
+// Host -> device update of engine state between ticks: ordered on the engine stream, so the next tick's kernels see
+// it (a plain hipMemcpy runs on the null stream, which a non-blocking stream does not wait for), and finished before
+// returning (the source is often a stack or vector buffer)
+inline hipError_t h2d(hipStream_t st, void* dst, const void* src, size_t bytes) {
+  hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+  return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+
+// create.hip
+int create(const swim_config* cfg, const swim_shard_spec* spec, swim_handle** out);
+bool delay_table(uint32_t D, uint32_t T, std::vector<uint32_t>* out);
+bool to_ticks(uint32_t ms, uint32_t tick, uint32_t* out);
+// api.hip
+int check_err(swim_handle* h);
+int push_epoch(swim_handle* h);
+// grow.hip
+int grow_caps(swim_handle* h);
+int grow_caps_shard(swim_handle* h);
+// exchange.hip
+int exchange_inline(swim_handle* h, uint8_t* recv, uint64_t cap, unsigned long long* scnt, unsigned long long* rcnt,
+                    bool spec);
+int exchange_rest(swim_handle* h, uint8_t* send, uint8_t* recv, uint64_t cap);
+int exchange(swim_handle* h, uint8_t* send, uint8_t* recv, uint64_t cap, unsigned long long* scnt,
+             unsigned long long* rcnt, bool inline_packed);
+int held_allreduce(swim_handle* h);
+// diag.hip
+int stats_dump(swim_handle* h, uint32_t k);
+int exp_dump_member_cycles(swim_handle* h);
+int exp_dump_wave_clock(swim_handle* h);
+int exp_dump_gossip_work(swim_handle* h);
+int prof_prepare(swim_handle* h, uint32_t n);
+bool prof_timed(const swim_handle* h, uint64_t tick);
+int prof_accumulate(swim_handle* h, uint64_t first, uint32_t n);
+// group.hip
+int create_group(const swim_config* cfg, swim_handle** out);
+int group_step(swim_handle* h, uint32_t n);
+void group_destroy(swim_handle* h);
+
+#pragma GCC visibility pop
+}  // namespace swim

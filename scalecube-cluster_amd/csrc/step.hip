@@ -1,0 +1,232 @@
+// step.hip — swim_step: the tick loop and its four paths (one GPU: a tick, a speculative batch; row shards: a
+// speculative batch, a tick). The order of launches, event records, host waits and grow_caps calls on each path is
+// what the results and the timed path depend on; the dumps and the profile bookkeeping are in diag.hip.
+#include "handle.h"
+
+#include <algorithm>
+
+using namespace swim;
+
+namespace {
+
+// where a swim_step(h, n) call stands: tick h->tick is the i-th of the call
+struct Step {
+  uint32_t n;
+  uint32_t i = 0;
+  uint32_t nb = 0;        // a speculative batch ends at the next scrub tick: the call's ticks before nb
+  bool need_diff = true;  // W == 1: SYNC diff(k) not queued yet (it is queued with the previous tick when it can be)
+};
+
+// the event set of the call's idx-th tick, if that tick is timed
+const TickEvents* events_of(swim_handle* h, uint64_t tick, uint32_t idx) {
+  return prof_timed(h, tick) ? &h->prof[idx] : nullptr;
+}
+
+// P0 gossip creations before the member kernel: the user gossips queued by the host
+int upload_user_gossips(swim_handle* h, uint32_t k) {
+  const Dev& d = h->d;
+  const size_t pairs = h->ugq.size() / 2;
+  if (pairs > h->ug_cap) {
+    int rc;
+    dfree(h, h->ug_dev);
+    h->ug_dev = nullptr;
+    h->ug_cap = 0;
+    const size_t cap = std::max<size_t>(pairs, 1024);
+    if ((rc = dalloc(h, &h->ug_dev, 2 * cap)) != SWIM_OK) return rc;
+    h->ug_cap = cap;
+  }
+  HIPCK(hipMemcpyAsync(h->ug_dev, h->ugq.data(), h->ugq.size() * 8, hipMemcpyHostToDevice, h->stream));
+  launch_user_gossips(d, k, h->ug_dev, (uint32_t)pairs, h->stream);
+  HIPCK(hipStreamSynchronize(h->stream));  // the host queue is reused after this
+  h->ugq.clear();
+  return SWIM_OK;
+}
+
+// One GPU, speculative batch: while no gossip slot is in use the host need not look at the flag after every member
+// kernel. The rest of the call is queued as diff / member pairs with no host wait; the member kernel after which
+// a slot is in use raises d.halt, every later launch of the batch returns at once, and the host resumes after
+// that tick with the gossip plane.
+int spec_batch(swim_handle* h, Step& s) {
+  const Dev& d = h->d;
+  const uint32_t k = (uint32_t)h->tick, i = s.i, nb = s.nb;
+  for (uint32_t j = i; j < nb; ++j) {
+    const uint32_t kj = k + (j - i);
+    if (s.need_diff) launch_diff(d, kj, h->stream, events_of(h, kj, j), true);
+    launch_member(d, kj, h->stream, events_of(h, kj, j), true);
+    s.need_diff = j + 1 == nb;
+    if (!s.need_diff) launch_diff(d, kj + 1, h->stream, events_of(h, kj + 1ull, j + 1), true);
+  }
+  HIPCK(hipMemcpyAsync((void*)(h->hflag + 1), d.halt, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  const uint32_t hk = h->hflag[1];
+  if (hk == 0) {  // the whole batch ran
+    h->tick += nb - i;
+    s.i = nb;
+    h->gossip_ran = false;
+    return SWIM_OK;
+  }
+  const uint32_t kh = hk - 1u;  // member(kh) ran; the launches after it returned at once
+  if (kh < k || kh >= k + (nb - i)) return fail(h, SWIM_EDEVICE, "speculative batch: bad halt tick");
+  HIPCK(hipMemsetAsync(d.halt, 0, 4, h->stream));
+  const uint32_t ih = i + (kh - k);
+  // a speculative member launch publishes no flag (tick_flag): the slots in use after member(kh) are read here, so
+  // the first gossip plane after an idle stretch gets the same capacity check as every other one (grow_caps); the
+  // device copy of the flag word follows, so tick_flag keeps writing it only on a change
+  {
+    int32_t top = 0;
+    HIPCK(hipMemcpyAsync(&top, d.free_top, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    const uint32_t used = (uint32_t)((int32_t)d.SPR - top);
+    h->hflag[0] = used;
+    HIPCK(hipMemcpyAsync(d.hsh, &used, 4, hipMemcpyHostToDevice, h->stream));
+    int gr;
+    if ((gr = grow_caps(h)) != SWIM_OK) return gr;
+  }
+  launch_gossip(d, kh, h->stream, events_of(h, kh, ih));
+  h->gossip_idle = false;
+  h->gossip_ran = true;
+  s.need_diff = true;  // diff(kh + 1) returned at once
+  h->tick = kh + 1ull;
+  s.i = ih + 1;
+  return SWIM_OK;
+}
+
+// One GPU, one tick: diff, member kernel, the host's look at the slots in use, the gossip plane if there are any
+int tick_one_gpu(swim_handle* h, Step& s) {
+  const Dev& d = h->d;
+  const uint32_t k = (uint32_t)h->tick, i = s.i;
+  const TickEvents* te = events_of(h, h->tick, i);
+  // SYNC diff(k) was queued in the previous iteration, except for the first tick of this call
+  if (s.need_diff) launch_diff(d, k, h->stream, te);
+  launch_member(d, k, h->stream, te, false, h->gossip_ran && !d.fastp4);
+  const bool nosync = (d.exp & 256) != 0;  // timing experiment: no per-tick event (gossip plane never launched)
+  if (!nosync) HIPCK(hipEventRecord(h->ev_member, h->stream));
+  const bool pipe = i + 1 < s.n && !h->no_pipe;
+  if (pipe) launch_diff(d, k + 1, h->stream, events_of(h, k + 1ull, i + 1));  // overlaps the wait
+  s.need_diff = !pipe;
+  if (!nosync) HIPCK(hipEventSynchronize(h->ev_member));  // (a spin wait measured the same here: diff(k+1) hides the wake-up)
+  h->gossip_idle = !nosync && h->hflag[0] == 0;
+  if (!nosync && !h->gossip_idle) {  // slots, rings and receipt lists sized up before they can overflow
+    int gr;
+    if ((gr = grow_caps(h)) != SWIM_OK) return gr;
+  }
+  h->gossip_ran = !nosync && (h->hflag[0] != 0 || h->no_skip);
+  if (nosync) {
+  } else if (h->hflag[0] != 0 || h->no_skip) {
+    launch_gossip(d, k, h->stream, te);
+    int sr;
+    if (h->stats && (sr = stats_dump(h, k)) != SWIM_OK) return sr;
+  } else if (te && te->all) {
+    HIPCK(hipEventRecord((hipEvent_t)te->ev[4], h->stream));
+    HIPCK(hipEventRecord((hipEvent_t)te->ev[5], h->stream));
+  }
+  if (d.XW > 1) {  // slot sharding: the members' gossip counts, every tick (collective)
+    int xr;
+    if ((xr = held_allreduce(h)) != SWIM_OK) return xr;
+  }
+  h->tick++;
+  ++s.i;
+  return SWIM_OK;
+}
+
+// the rest of a row-sharded tick after its exchange A: B, the exchange of first receipts, C, growth
+int shard_tick_rest(swim_handle* h, uint32_t k, const TickEvents* te) {
+  const Dev& d = h->d;
+  int xr;
+  const bool gossip = h->xflag;
+  launch_tick_b(d, k, h->stream, te, gossip);
+  if (gossip && (xr = exchange(h, d.xb_send, d.xb_recv, d.XB_PEER, d.xb_scnt, d.xb_rcnt, false)) != SWIM_OK) return xr;
+  launch_tick_c(d, k, h->stream, gossip);
+  if (gossip && (xr = grow_caps_shard(h)) != SWIM_OK) return xr;
+  return SWIM_OK;
+}
+
+// Row shards, speculative batch: while no shard has a gossip slot in use and every exchange-A region fits its inline
+// block, a tick needs nothing from the host. The rest of the call is queued as A / inline all-to-all / B with
+// no host wait; the gate after the all-to-all of the first tick that needs the host (the same tick on every
+// shard: the flags ride on the exchanged count words) raises d.halt, every later launch returns at once (the
+// all-to-alls still run, carrying nothing anyone reads), and the host finishes that tick on the normal path.
+int shard_spec_batch(swim_handle* h, Step& s) {
+  const Dev& d = h->d;
+  const uint32_t k = (uint32_t)h->tick, i = s.i, nb = s.nb;
+  int xr;
+  for (uint32_t j = i; j < nb; ++j) {
+    const uint32_t kj = k + (j - i);
+    const TickEvents* tj = events_of(h, kj, j);
+    launch_tick_a(d, kj, h->stream, tj, true);
+    if ((xr = exchange_inline(h, d.xa_recv, d.XA_PEER, d.xa_scnt, d.xa_rcnt, true)) != SWIM_OK) return xr;
+    launch_tick_b(d, kj, h->stream, tj, false, true);
+  }
+  HIPCK(hipMemcpyAsync((void*)(h->hflag + 1), d.halt, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  const uint32_t hk = h->hflag[1];
+  if (hk == 0) {
+    h->tick += nb - i;
+    s.i = nb;
+    return SWIM_OK;
+  }
+  const uint32_t kh = hk - 1u;  // tick kh ran up to its inline exchange; the launches after that returned at once
+  if (kh < k || kh >= k + (nb - i)) return fail(h, SWIM_EDEVICE, "speculative sharded batch: bad halt tick");
+  HIPCK(hipMemsetAsync(d.halt, 0, 4, h->stream));
+  const uint32_t ih = i + (kh - k);
+  if ((xr = exchange_rest(h, d.xa_send, d.xa_recv, d.XA_PEER)) != SWIM_OK) return xr;
+  if ((xr = shard_tick_rest(h, kh, events_of(h, kh, ih))) != SWIM_OK) return xr;
+  h->tick = kh + 1ull;
+  s.i = ih + 1;
+  return SWIM_OK;
+}
+
+// Row shards, one tick: A, exchange A (the host waits for it: the gossip flag and the sizes), then the rest
+int shard_tick(swim_handle* h, Step& s) {
+  const Dev& d = h->d;
+  const uint32_t k = (uint32_t)h->tick;
+  const TickEvents* te = events_of(h, h->tick, s.i);
+  int xr;
+  launch_tick_a(d, k, h->stream, te);
+  if ((xr = exchange(h, d.xa_send, d.xa_recv, d.XA_PEER, d.xa_scnt, d.xa_rcnt, true)) != SWIM_OK) return xr;
+  if ((xr = shard_tick_rest(h, k, te)) != SWIM_OK) return xr;
+  h->tick++;
+  ++s.i;
+  return SWIM_OK;
+}
+
+}  // namespace
+
+extern "C" int swim_step(swim_handle* h, uint32_t n) {
+  if (!h) return SWIM_EINVAL;
+  if (h->grp) return group_step(h, n);
+  hipSetDevice((int)h->cfg.device);
+  if (h->tick + n >= (1ull << 28)) return SWIM_ECAPACITY;  // deadlines are stored in 29 bits
+  int rc;
+  if ((rc = prof_prepare(h, n)) != SWIM_OK) return rc;
+  const uint64_t first = h->tick;
+  const Dev& d = h->d;
+  const bool no_batch = d.churn || h->no_spec || (h->cfg.flags & SWIM_FLAG_PROFILE_ALL);  // (PROFILE_ALL times every tick's gossip plane)
+  Step s{n};
+  while (s.i < n) {
+    const uint32_t k = (uint32_t)h->tick;
+    if (h->tick >= h->next_scrub) {  // stale holder entries of recycled slots, before they can alias (engine.h)
+      launch_s_scrub(d, k, h->stream);
+      h->next_scrub = h->tick + SCRUB;
+    }
+    s.nb = (uint32_t)std::min<uint64_t>(n, s.i + (h->next_scrub - h->tick));
+    // P0 gossip creations before the member kernel: RUMOR-mode churn rumors, then the user gossips queued by the host
+    if (d.churn && k % d.ping_t == 0) launch_churn(d, k, h->stream);
+    if (s.i == 0 && !h->ugq.empty() && (rc = upload_user_gossips(h, k)) != SWIM_OK) return rc;
+    if (d.W == 1 && h->gossip_idle && s.i + 1 < s.nb && d.XW == 1 && !h->no_pipe && !h->no_skip && !no_batch)
+      rc = spec_batch(h, s);
+    else if (d.W == 1)
+      rc = tick_one_gpu(h, s);
+    else if (h->spec.transport == SWIM_TRANSPORT_RCCL && !h->xflag && s.i + 1 < s.nb && !no_batch)
+      rc = shard_spec_batch(h, s);
+    else
+      rc = shard_tick(h, s);
+    if (rc != SWIM_OK) return rc;
+  }
+  rc = check_err(h);
+  if (rc == SWIM_OK && (d.exp & (16 | 128))) rc = exp_dump_member_cycles(h);
+  if (rc == SWIM_OK && (d.exp & 512)) rc = exp_dump_wave_clock(h);
+  if (rc == SWIM_OK && (d.exp & 4)) rc = exp_dump_gossip_work(h);
+  if (rc == SWIM_OK) rc = prof_accumulate(h, first, n);
+  return rc;
+}

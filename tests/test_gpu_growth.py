@@ -1,4 +1,4 @@
-"""Capacity growth between ticks (api.hip grow_caps): the gossip slot table, the receipt rings and the per-tick receipt
+"""Capacity growth between ticks (grow.hip grow_caps): the gossip slot table, the receipt rings and the per-tick receipt
 and replay lists start far too small and are grown, contents moved, before they can overflow. The golden scenarios
 (recorded from the oracle, which has no capacities) replay bit for bit, and the handle ends with more device memory
 than it started with."""
@@ -16,6 +16,15 @@ GOLDEN = Path(__file__).resolve().parent / "golden"
 pytestmark = pytest.mark.gpu
 
 
+# the structures each scenario outgrows from these tiny sizes (swim_debug_caps names); the others keep their size
+GROWN = {
+    "c2_small": {"slots", "ring", "replay"},
+    "c4_mid": {"slots", "ring", "receipts", "replay", "history"},
+    "c2_mid": {"slots", "ring", "receipts", "replay", "history"},
+    "c4_long": {"slots", "ring", "receipts", "replay"},
+}
+
+
 @pytest.mark.parametrize("name", ["c2_small", "c4_mid", "c2_mid", "c4_long"])
 def test_golden_with_growing_caps(engine, monkeypatch, name):
     import sys
@@ -27,6 +36,7 @@ def test_golden_with_growing_caps(engine, monkeypatch, name):
     cfg = dataclasses.replace(cfg, gossip_slot_cap=256, gossip_ring_cap=256)
     c = SimulatedCluster(engine, cfg)
     b0 = c.counters()["device_bytes"]
+    caps0 = _abi.debug_caps(c.lib, c._h)
     rec = record(c, name)
     b1 = c.counters()["device_bytes"]
     caps = _abi.debug_caps(c.lib, c._h)
@@ -35,8 +45,11 @@ def test_golden_with_growing_caps(engine, monkeypatch, name):
     assert len(rec["periods"]) == len(want["periods"])
     for got, exp in zip(rec["periods"], want["periods"]):
         assert got == exp, f"{name} period {exp['period']}: {got} != {exp}"
+    print(f"{name}: device bytes {b0} -> {b1}, caps {caps0} -> {caps}", flush=True)
     assert b1 > b0 and caps["growths"] > 0, "no capacity grew"
-    print(f"{name}: device bytes {b0} -> {b1}, caps {caps}", flush=True)
+    structures = [k for k in caps if k != "growths"]
+    assert all(caps[k] >= caps0[k] for k in structures), (caps0, caps)
+    assert {k for k in structures if caps[k] > caps0[k]} == GROWN[name], (caps0, caps)
 
 
 def test_growth_off_overflows(engine, monkeypatch):
@@ -66,7 +79,7 @@ def test_rumor_defaults_from_churn(engine):
 @pytest.mark.parametrize("name", ["c2_mid", "c4_long"])
 def test_sharded_golden_with_growing_rings(engine, name):
     """Row-sharded handles (2 shards) grow their receipt rings and incarnation history between gossip ticks
-    (api.hip grow_caps_shard): the rings start at 256 entries, the peers' first receipts count towards the fill
+    (grow.hip grow_caps_shard): the rings start at 256 entries, the peers' first receipts count towards the fill
     (k_unpack_b), and the golden replays bit for bit with more device memory at the end."""
     import sys
     sys.path.insert(0, str(GOLDEN))

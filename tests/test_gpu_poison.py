@@ -43,3 +43,22 @@ def test_poisoned_cold_join_partition(oracle, engine, poisoned):
         c.unblock_all()
     run_lockstep(o, e, 200, 50, "poisoned heal")
     e.close()
+
+
+@pytest.mark.parametrize("var", ["SWIM_GUARD", "SWIM_POISON"])
+def test_smoke_shape_guarded_or_poisoned(oracle, engine, monkeypatch, var):
+    """The allocation debugging aids through the device-allocation registry (dev_alloc.h): a 64-member cold join, 100
+    ticks with a kill (smoke()'s shape), every allocation between guard zones (checked after every step) or
+    poisoned: state hashes and events identical to the oracle's, and no error from the guard walk."""
+    monkeypatch.setenv(var, "1")
+    cfg = SimConfig(n_members=64, cluster=ClusterConfig(seedMembers=[0]), init_mode=_abi.INIT_COLD_JOIN,
+                    record_events=True)
+    o, e = pair(oracle, engine, cfg)
+    monkeypatch.delenv(var)  # read when the handle is made
+    run_lockstep(o, e, 60, 60, f"{var} join", events=False)
+    for c in (o, e):
+        c.kill(63)
+    ev = run_lockstep(o, e, 40, 40, f"{var} kill")
+    assert len(ev) > 0
+    e.sync()  # check_err: guards intact, no error bits
+    e.close()

@@ -1,4 +1,4 @@
-"""Speculative batches and host-queued gossips (api.hip swim_step, dev_util.h tick_reset).
+"""Speculative batches and host-queued gossips (step.hip swim_step, dev_util.h tick_reset).
 
 While no gossip slot is in use, one swim_step call is queued as SYNC-diff / member-kernel pairs with no host wait, and the
 member kernel after which the gossip plane is needed raises the batch halt. User gossips (Cluster.spreadGossip,

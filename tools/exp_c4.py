@@ -9,7 +9,7 @@ sys.path.insert(0, str(ROOT / "scalecube-cluster_amd"))
 import os  # noqa: E402
 
 # the DEAD-gossip storm delivers ~10^8 first receipts a tick; the engine grows its slot table, receipt rings and
-# per-tick receipt lists as the storm builds (api.hip grow_caps), so no capacity is set here unless asked for
+# per-tick receipt lists as the storm builds (grow.hip grow_caps), so no capacity is set here unless asked for
 import swimhip  # noqa: E402
 from swimhip import ClusterConfig, SimConfig  # noqa: E402
 
