@@ -78,6 +78,23 @@ int swim_debug_holders(swim_handle* h, uint32_t first, uint32_t n, uint32_t* out
  * SYNC_ACK that m sent in the last tick still carries m's live row as its payload. */
 int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc);
 
+/* One GPU, stored tables: the SYNC diff skips the 2048-subject chunks of a live-row payload that neither the sender's
+ * nor the receiver's row ever changed against the baseline row. SWIM_NO_DIRTY=1, read by swim_create,
+ * keeps the rows' dirty-chunk masks up to date but never consults them: every chunk is streamed (the reference path
+ * of the equality tests, and A/B timing on one build).
+ * swim_debug_diff_dirty: n <= 8 entries since create; the last one costs a pass over the key plane. */
+#define SWIM_DD_SKIPPED 0u      /* narrow chunks decided from the masks, not streamed */
+#define SWIM_DD_STREAMED 1u     /* narrow chunks streamed */
+#define SWIM_DD_MSG_SKIPPED 2u  /* payloads decided without streaming any chunk */
+#define SWIM_DD_REBASES 3u      /* baseline chunks replaced (k_rebase) */
+#define SWIM_DD_DIRTY_ROWS 4u   /* (row, chunk) pairs marked dirty now */
+int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n);
+
+/* the masks' invariant, tested directly: the number of (row, chunk) pairs marked clean whose keys differ from the
+ * baseline's chunk, which on one GPU is what the first row marked clean in that chunk holds: all clean rows must agree
+ * (0 in a correct engine). One pass over the key plane. */
+int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
+
 #ifdef __cplusplus
 }
 #endif

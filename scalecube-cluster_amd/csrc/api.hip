@@ -717,9 +717,14 @@ int swim_counters_get(swim_handle* h, swim_counters* out) {
   out->diff_msgs_total = c[C_DIFFMSG_ALL];
   // the payloads streamed from the 8-bit shadow plane compared 2 B per subject, the others (C_DIFFWIDE) 8 B
   const uint64_t nsub = h->d.N;
-  out->diff_key_bytes = nsub * (2 * (c[C_DIFFMSG] - std::min(c[C_DIFFMSG], c[C_DIFFWIDE])) + 8 * c[C_DIFFWIDE]);
-  out->diff_key_bytes_total =
-      nsub * (2 * (c[C_DIFFMSG_ALL] - std::min(c[C_DIFFMSG_ALL], c[C_DIFFWIDE_ALL])) + 8 * c[C_DIFFWIDE_ALL]);
+  if (h->d.W == 1 && h->d.MW) {  // one GPU: the narrow chunks actually streamed (the others: decided from the dirty masks)
+    out->diff_key_bytes = 2 * c[C_DSUBJ] + 8 * nsub * c[C_DIFFWIDE];
+    out->diff_key_bytes_total = 2 * c[C_DSUBJ_ALL] + 8 * nsub * c[C_DIFFWIDE_ALL];
+  } else {
+    out->diff_key_bytes = nsub * (2 * (c[C_DIFFMSG] - std::min(c[C_DIFFMSG], c[C_DIFFWIDE])) + 8 * c[C_DIFFWIDE]);
+    out->diff_key_bytes_total =
+        nsub * (2 * (c[C_DIFFMSG_ALL] - std::min(c[C_DIFFMSG_ALL], c[C_DIFFWIDE_ALL])) + 8 * c[C_DIFFWIDE_ALL]);
+  }
   out->exchange_ns = (uint64_t)(h->xchg_ms * 1e6);
   return SWIM_OK;
 }
@@ -767,6 +772,25 @@ int swim_debug_holders(swim_handle* h, uint32_t first, uint32_t n, uint32_t* out
   return SWIM_OK;
 }
 
+// one pass over the key plane: the clean (row, chunk) pairs that differ from the chunk's first clean row, and the
+// dirty pairs
+static int dirty_check(swim_handle* h, uint32_t* viol, uint64_t* dirty) {
+  uint32_t* buf = nullptr;
+  HIPCK(hipMalloc(&buf, 8 + 4ull * h->d.NCHUNK));
+  hipError_t e = hipMemsetAsync(buf, 0, 8, h->stream);
+  uint32_t r[2] = {0, 0};
+  if (e == hipSuccess) {
+    launch_dirty_check(h->d, buf, buf + 1, buf + 2, h->stream);
+    e = hipStreamSynchronize(h->stream);
+  }
+  if (e == hipSuccess) e = hipMemcpy(r, buf, 8, hipMemcpyDeviceToHost);
+  hipFree(buf);
+  HIPCK(e);
+  *viol = r[0];
+  *dirty = r[1];
+  return SWIM_OK;
+}
+
 int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc) {
   if (!h) return SWIM_EINVAL;
   if (h->grp || h->d.W > 1) return SWIM_EUNSUPPORTED;
@@ -787,16 +811,39 @@ int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc) {
         return SWIM_EINVAL;
       }
   }
-  uint32_t* w = d.rowk + lidx(d, m) * d.NS + m;
   uint32_t k = 0;
-  HIPCK(hipMemcpy(&k, w, 4, hipMemcpyDeviceToHost));
-  k = (inc << 2) | (k & 3u);
-  HIPCK(hipMemcpy(w, &k, 4, hipMemcpyHostToDevice));
-  if (d.rowk8) {
-    const uint8_t k8 = key8(k);
-    HIPCK(hipMemcpy(d.rowk8 + lidx(d, m) * d.NS8 + m, &k8, 1, hipMemcpyHostToDevice));
-  }
+  HIPCK(hipMemcpy(&k, d.rowk + lidx(d, m) * d.NS + m, 4, hipMemcpyDeviceToHost));
+  launch_key_set(d, m, m, (inc << 2) | (k & 3u), h->stream);  // (the key, its shadow and the row's dirty mask)
+  HIPCK(hipStreamSynchronize(h->stream));
   return SWIM_OK;
+}
+
+int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n) {
+  if (!h || !out || n > 8) return SWIM_EINVAL;
+  if (h->grp || h->d.W > 1 || !h->d.MW) return SWIM_EUNSUPPORTED;
+  const Dev& d = h->d;
+  HIPCK(hipStreamSynchronize(h->stream));
+  unsigned long long c[C_NCTR];
+  HIPCK(hipMemcpy(c, d.ctr, sizeof(c), hipMemcpyDeviceToHost));
+  // every narrow payload (listed or decided by the lister) has NCHUNK chunks: streamed or skipped
+  const unsigned long long narrow = c[C_DIFFMSG_ALL] - std::min(c[C_DIFFMSG_ALL], c[C_DIFFWIDE_ALL]);
+  uint32_t viol = 0;
+  uint64_t dirty = 0;
+  int rc;
+  if (n > SWIM_DD_DIRTY_ROWS && (rc = dirty_check(h, &viol, &dirty)) != SWIM_OK) return rc;
+  const uint64_t v[5] = {narrow * d.NCHUNK - c[C_DSTREAM], c[C_DSTREAM], c[C_DMSGSKIP], h->rebases, dirty};
+  for (size_t i = 0; i < n; ++i) out[i] = i < 5 ? v[i] : 0;
+  return SWIM_OK;
+}
+
+int swim_debug_dirty_check(swim_handle* h, uint64_t* violations) {
+  if (!h || !violations) return SWIM_EINVAL;
+  if (h->grp || h->d.W > 1 || !h->d.MW) return SWIM_EUNSUPPORTED;
+  uint32_t viol = 0;
+  uint64_t dirty = 0;
+  const int rc = dirty_check(h, &viol, &dirty);
+  *violations = viol;
+  return rc;
 }
 
 // debugging aid (not part of the ABI header): the gossip send log of SWIM_SEND_LOG (tick, sender, gid lo/hi, target)

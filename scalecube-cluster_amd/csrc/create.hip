@@ -34,7 +34,7 @@ bool to_ticks(uint32_t ms, uint32_t tick, uint32_t* out) {
 
 // SWIM_CAPS="trk=1,ulog=2,creq=1,cwmax=1,cev=1,mq=1,sort=2,..." (include/swimhip_debug.h), parsed once at create: lowers
 // the fast structures' capacities in d (already at their defaults); rx= and rp= size allocations
-static void parse_caps(const char* caps, Dev& d, uint32_t* rx_cap, uint32_t* rp_cap) {
+static void parse_caps(const char* caps, Dev& d, uint32_t* rx_cap, uint32_t* rp_cap, uint32_t* rb_thr, uint32_t* rb_int) {
   std::string s(caps);
   size_t p = 0;
   while (p < s.size()) {
@@ -54,6 +54,8 @@ static void parse_caps(const char* caps, Dev& d, uint32_t* rx_cap, uint32_t* rp_
     else if (k == "cev") d.cev_cap = clampv(0, CEV);
     else if (k == "mq") d.mq_cap = clampv(1, MQ);
     else if (k == "hv") d.hv = std::max<uint32_t>(1, v);  // k_inbox_apply from this many receipts
+    else if (k == "rbt") *rb_thr = std::max<uint32_t>(1, v);  // rebase a chunk after this many wasted compares
+    else if (k == "rbi") *rb_int = std::max<uint32_t>(1, v);  // ... looked at every this many ticks
     else if (k == "rx") *rx_cap = v;
     else if (k == "rp") *rp_cap = std::max<uint32_t>(64, v);  // replay / slow-path send lists (grow_caps tests)
     else if (k == "xinl") d.XI = std::max<uint32_t>(64, std::min<uint32_t>(XINL, v)) & ~7u;  // send/recv group past it
@@ -114,11 +116,12 @@ static int fill_dev(swim_handle* h) {
   d.ULOGC = c.n_members <= 65536 ? ULOG : 256;
   d.trk_cap = TRK, d.ulog_cap = d.ULOGC, d.creq_cap = CREQ, d.cwmax_cap = CWMAX, d.cev_cap = CEV, d.mq_cap = MQ;
   d.rr_atomic = getenv("SWIM_RR_ATOMIC") ? (uint32_t)atoi(getenv("SWIM_RR_ATOMIC")) : 64u;  // (measurements)
+  h->rb_thr = 0, h->rb_int = REBASE_CHECK;
   d.hv = 24;  // routed receipts from which a member's P4 runs on a wave of its own (k_inbox_apply)
   d.XI = XINL;
   d.sort_cap = SORT_MAX;
   uint32_t rx_cap = NEVER, rp_cap = 0;
-  if (const char* caps = getenv("SWIM_CAPS")) parse_caps(caps, d, &rx_cap, &rp_cap);
+  if (const char* caps = getenv("SWIM_CAPS")) parse_caps(caps, d, &rx_cap, &rp_cap, &h->rb_thr, &h->rb_int);
   h->rx_pinned = rx_cap != NEVER;  // (growth keeps the pin: the variable may be gone by then)
   // seeds: LinkedHashSet of valid ids (MembershipProtocolImpl.java:160-166); self is skipped per member
   for (uint32_t i = 0; i < c.n_seeds; ++i) {
@@ -261,6 +264,14 @@ static int fill_dev(swim_handle* h) {
     d.DSCAP = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, (256ull << 20) / (4ull * d.NS)));
   }
   if (getenv("SWIM_SEND_LOG")) d.dbg_send_cap = (uint32_t)atoi(getenv("SWIM_SEND_LOG"));  // debugging aid: every counted gossip send
+  // one GPU, stored tables: the rows' dirty-chunk masks decide SYNC-diff chunks without a load (k_ack_resolve);
+  // SWIM_NO_DIRTY keeps the masks but never consults them (measurements, and the tests' reference path)
+  // (RUMOR mode sends no SYNC: no masks)
+  // the masks and the rebase counters live in the members' records' spare words (MS), no allocation of their own
+  if (d.W == 1 && !d.implicit && d.mode != SWIM_MODE_RUMOR && (d.NCHUNK + 63) / 64 <= MSW) {
+    d.MW = (d.NCHUNK + 63) / 64;
+    if (d.ackres && !getenv("SWIM_NO_DIRTY")) d.ackres |= ACKRES_DIRTY;
+  }
   if (d.W > 1) {
     d.MW = (d.NCHUNK + 63) / 64;
     d.NSCAP = 1u << 16;
@@ -335,7 +346,9 @@ static int alloc_table(swim_handle* h) {
   A(d.hv_list, NL) Z(d.nhv, 1) A(d.hv_pend, NL) A(d.hv_tlast, NL) A(d.sg_list, N) A(d.nsg, 1) A(d.ap_list, N) A(d.nap, 1)
   Z(d.tbm, NL * d.NW)
   if (d.ackres) {
-    A(d.tlog, 2 * NL * TL) A(d.tl_n, 2 * NL) F(d.tl_tick, 2 * NL) A(d.dlist, 4ull * d.MSGCAP) Z(d.ndl, 1)
+    A(d.tlog, 2 * NL * TL) A(d.tl_n, 2 * NL) F(d.tl_tick, 2 * NL) Z(d.ndl, 1)
+    // (one GPU: an entry per narrow item, engine.h NPER)
+    A(d.dlist, 4ull * d.MSGCAP * (d.W == 1 ? (d.NCHUNK + NPER - 1) / NPER : 1u))
     A(d.dlist_w, 4ull * d.MSGCAP) Z(d.ndlw, 1)
     if (d.W > 1) A(d.mlog, (uint64_t)d.MSGCAP * TL)
   }

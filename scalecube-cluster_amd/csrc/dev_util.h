@@ -317,6 +317,35 @@ __device__ __forceinline__ void pin_msg(const Dev& d, uint32_t b, uint32_t j) {
   atomicCAS(p, NEVER, r);
 }
 
+// Every store to the key plane goes through key_put: key k of subject s into the row rk (local index li), its 8-bit
+// shadow, and the row's dirty-chunk mask rd (row_dirty; null: none kept). The mask's invariant is "bit clear => the
+// chunk of the row equals the baseline's chunk" (one GPU: the chunk every other clean row holds; no baseline row is
+// stored there). On a row shard the bit is set when the key differs from base_row (that limits what a payload ships);
+// on one GPU by any key change (old: the key replaced), without a baseline load.
+// mark = false: the caller sets the bits of the whole wave's writes itself (dirty_mark_wave).
+__device__ __forceinline__ void dirty_mark(uint64_t* rd, uint32_t s) {
+  uint64_t* w = rd + ((s / CH) >> 6);
+  const uint64_t bit = 1ull << ((s / CH) & 63), o = *w;
+  if (!(o & bit)) *w = o | bit;
+}
+__device__ __forceinline__ void key_put(const Dev& d, uint32_t* rk, uint64_t* rd, size_t li, uint32_t s, uint32_t k,
+                                        uint32_t old, bool mark = true) {
+  rk[s] = k;
+  if (d.rowk8) d.rowk8[li * d.NS8 + s] = key8(k);
+  if (mark && rd && (d.W > 1 ? k != d.base_row[s] : k != old)) dirty_mark(rd, s);
+}
+// a wave that owns the row: the lanes with wr set stored a changed key of subject s with key_put(mark = false); lane 0
+// sets the bit of each distinct chunk among them
+__device__ __forceinline__ void dirty_mark_wave(uint64_t* rd, bool wr, uint32_t s) {
+  if (!rd) return;
+  const uint32_t c = s / CH;
+  for (unsigned long long wm = __ballot(wr); wm;) {
+    const uint32_t co = __shfl(c, (int)(__ffsll((long long)wm) - 1));
+    if ((threadIdx.x & 63u) == 0) dirty_mark(rd, co * CH);
+    wm &= ~__ballot(wr && c == co);
+  }
+}
+
 // key32 of subject s in payload mm (messages of buffer b): its copy-on-write snapshot, its pinned copy, or a
 // payload received from another shard (shipped chunk or baseline row). Only for payloads that are immutable now.
 __device__ __forceinline__ uint32_t payload_key_at(const Dev& d, const SyncMsg& mm, uint32_t b, uint32_t s) {

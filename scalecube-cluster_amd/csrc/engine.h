@@ -44,6 +44,7 @@ constexpr uint32_t S_TICK_MASK = (1u << 29) - 1u;
 // entries of recycled slots, so a stale entry is at most SLIFE + SCRUB < 8192 - lat ticks old
 constexpr uint16_t S16_REBORN = 1u << 15, S16_SWEPT = 1u << 14, S16_EVER = 1u << 13, S16_TICK = (1u << 13) - 1u;
 constexpr uint32_t SLIFE = 4096, SCRUB = 2048;
+constexpr uint32_t REBASE_CHECK = 16;  // ticks between two looks at the rebase counters (swim_handle::rb_int)
 // the creation tick of a stored entry: the latest tick at or before ref (the newest an entry can carry: now + lat)
 // with the stored low 13 bits
 __host__ __device__ __forceinline__ uint32_t s16_tick(uint16_t e, uint32_t ref) {
@@ -89,7 +90,12 @@ constexpr uint32_t XINL = 16384;  // RCCL: bytes per peer moved by the fixed-siz
 // counters (swim_counters order after .tick)
 // 8..12: SWIM_EXP & 4 (and 16..19: the gossip plane's work units per tick, for algorithmic bytes; tools/pmc_gossip.py)
 constexpr uint32_t CSH = 64, CSTRIDE = 64;  // Dev::ctr_sh rows, 512 B apart
-enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29 };
+enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29,
+           // dirty-chunk skipping of the SYNC diff (one GPU): narrow 2048-subject chunks the lister had
+           // streamed, their subjects over the timed and over all launches (2 B each in swim_counters.diff_key_bytes*),
+           // narrow payloads decided without a stream. (The chunks skipped follow: every narrow payload, C_DIFFMSG_ALL
+           // less C_DIFFWIDE_ALL, has NCHUNK of them.)
+           C_DSTREAM = 20, C_DSUBJ = 21, C_DSUBJ_ALL = 22, C_DMSGSKIP = 23 };
 
 // capacity fallbacks that fired (include/swimhip_debug.h; counted only when Dev::fb is allocated: SWIM_CAPS or
 // SWIM_FALLBACKS set at create). Each one is an exact slow path taken when a fixed-capacity fast structure is full.
@@ -129,6 +135,9 @@ constexpr uint32_t KF_RES = 0x400u;
 // is the message's payload (arena row or PAY_RX | rx index), NEVER for the live row, DESC_PIN | arena row for a pinned
 // live row, DESC_DEFER for a delayed message (kernels.hip desc_pay)
 constexpr uint32_t DESC_PIN = 0x80000000u, DESC_DEFER = 0xFFFFFFFEu;
+// On one GPU the narrow list holds one entry per item (four chunks of one message) with a chunk to stream, and the
+// fourth word is item index << 4 | the item's chunks to stream (k_ack_resolve; the others are known equal, Dev::rdirty)
+constexpr uint32_t NPER = 4;  // chunks per narrow item
 constexpr uint32_t KF_LATE = 0x800u;  // a delayed message put back by k_sync_redeliver
 constexpr uint32_t KF_FLAGS = KF_DEFER | KF_ABS | KF_RES | KF_LATE;
 constexpr uint32_t TL = 16;  // per-member tick write log (ack resolution); past it the member's ACKs are streamed
@@ -143,8 +152,14 @@ struct alignas(16) MS {
   uint32_t nsub, npath, nfetch, fnext;  // fnext: earliest tick at which a pending metadata fetch needs the member
   int32_t pingIdx, remoteIdx;
   uint64_t evHash;
-  uint32_t pad[12];
+  // the record's spare words, written by no load or store of the member's state (those move the first 80 B).
+  // One GPU, stored tables: dirty = the row's dirty-chunk mask (Dev::MW <= MSW words; DESIGN.md §3.1, row_dirty);
+  // cstat of member c = the rebase policy's counters of chunk c (every cluster has at least as many members as
+  // chunks): compares of the chunk streamed / found different since its last rebase, and a sender of it (k_rebase)
+  uint64_t dirty[3];
+  unsigned long long cstat[3];
 };
+constexpr uint32_t MSW = 3;  // mask words a member record holds: 196 608 members, more than a stored table can have
 static_assert(sizeof(MS) == 128, "one cache line per member");
 
 struct Dev {
@@ -328,11 +343,12 @@ struct Dev {
   // SYNC_ACK resolution (W == 1): per member and tick parity, the subjects whose key its row changed in
   // that tick plus the candidates of the payloads it merged (first TL of them), their count (> TL: overflowed) and the
   // tick they belong to; the messages k_sync_diff streams this tick (the others are resolved)
-  uint32_t ackres;
+  uint32_t ackres;    // 0: every payload streamed; ACKRES_ON, | ACKRES_DIRTY: k_ack_resolve consults rdirty (W == 1)
   uint32_t* tlog;     // [2][NL][TL]
   uint32_t* tl_n;     // [2][NL]
   uint32_t* tl_tick;  // [2][NL]
-  uint32_t* dlist;    // [MSGCAP] 16-B entries: payloads k_sync_diff streams from the 8-bit plane (k_ack_resolve)
+  uint32_t* dlist;    // [MSGCAP] 16-B entries: payloads k_sync_diff streams from the 8-bit plane (k_ack_resolve);
+                      // W == 1: [MSGCAP][NCHUNK / NPER rounded up], an entry per item
   uint32_t* dlist_w;  // [MSGCAP] 16-B entries: payloads it streams on 4-B keys
   uint32_t* ndlw;
   uint32_t* ndl;
@@ -360,7 +376,8 @@ struct Dev {
   uint32_t* hflag;          // host-mapped: [0] gossip slots in use after this tick's member control (W == 1);
                             // [1] the halt tick read back after a speculative batch; with rfill: the previous gossip
                             // plane's largest receipt-ring fill [2], routed receipts [3], replay and slow-path sends
-                            // [4], [5], history entries in use [6]
+                            // [4], [5], history entries in use [6]; [7] a narrow chunk was streamed since the
+                            // host's last look at the rebase counters (k_ack_resolve)
   uint32_t* hsh;            // [8] device copy of what hflag holds (tick_flag writes host memory only on a change):
                             // hsh[0] mirrors hflag[0], hsh[1..5] mirror hflag[2..6]
   uint32_t* rfill;          // [1] W == 1: largest ring fill (rtail - rhead) after this tick's receipts (grow_caps)
@@ -381,9 +398,15 @@ struct Dev {
   uint32_t NSCAP, RRCAP, RQCAP, RXCAP, CHCAP;
   uint64_t XA_PEER, XB_PEER;  // bytes per peer region of the two exchange buffers
   uint64_t* rdirty;    // [NL][MW] per own observer: the 2048-record chunks of its key plane ever written with a key
-                       // that differs from base_row (conservative: never cleared); a payload ships exactly these
+                       // that differs from base_row (conservative: never cleared); a payload ships exactly these.
+                       // One GPU (stored tables, MW != 0): the masks live in the members' records (MS::dirty,
+                       // row_dirty) and rdirty is null; there a clear bit means "equal to every other row's chunk
+                       // whose bit is clear", so a bit clear in the sender's and in the receiver's row decides the
+                       // chunk's compares without a load (k_ack_resolve, when ackres has ACKRES_DIRTY); set by every
+                       // key change (key_put), recomputed by k_rebase
   uint64_t* arena_dirty[2];  // [ARENA_ROWS][MW] the sender's rdirty at copy-on-write time
   uint32_t* base_row;  // [NS] baseline key plane: a remote SYNC payload ships only its chunks that differ
+                       // (W == 1: not stored; the baseline is what the clean chunks of the rows all hold)
   uint8_t* base_row8;  // [NS8] with rowk8: base_row's 8-bit shadow (narrow items of peers' payloads)
   uint32_t* xn;        // [8] 0 new slots, 1 round records, 2 sweeps, 4 inbound msgs (mtmp), 5 rx payloads
   uint32_t* ns_rec;    // [NSCAP][NSW] gossips created on this shard this tick
@@ -418,6 +441,13 @@ struct Dev {
   unsigned long long* evp_hash;  // [N]
   uint32_t* evp_n;               // [N]
 };
+
+constexpr uint32_t ACKRES_ON = 1, ACKRES_DIRTY = 2;
+// the dirty-chunk mask of the row at local index li (MW words), or null when none is kept
+__host__ __device__ __forceinline__ uint64_t* row_dirty(const Dev& d, size_t li) {
+  if (!d.MW) return nullptr;
+  return d.W > 1 ? d.rdirty + li * d.MW : d.ms[li].dirty;
+}
 
 // PRECONVERGED list w (0: pingMembers, 1: remoteMembers) of observer m: position p holds the other member of rank
 // feistel(p) (SEMANTICS.md §3; k_init_lists, and computed on the fly with implicit views)
@@ -490,6 +520,13 @@ void launch_s_scrub(const Dev& d, uint32_t now, void* stream);  // every SCRUB t
 void launch_ring_move(const uint32_t* rg, uint32_t* rg2, const uint32_t* rhead, const uint32_t* rtail, uint32_t N,
                       uint32_t B, uint32_t B2, void* stream);  // capacity growth of the receipt rings
 void launch_hist_rehash(const uint64_t* h1, uint32_t cap1, uint64_t* h2, uint32_t cap2, void* stream);
+// one GPU, between ticks: baseline chunk c := chunk c of row r, every row's dirty bit c recomputed (k_rebase)
+void launch_rebase(const Dev& d, uint32_t c, uint32_t r, void* stream);
+// one GPU: a host write of one key (swim_debug_set_incarnation), through key_put
+void launch_key_set(const Dev& d, uint32_t m, uint32_t s, uint32_t key, void* stream);
+// one GPU: the masks' invariant (swim_debug_dirty_check): the clean (row, chunk) pairs that differ from the first clean
+// row's chunk counted into *viol, the set bits of the masks summed into *ndirty; ref: [NCHUNK] scratch
+void launch_dirty_check(const Dev& d, uint32_t* viol, uint32_t* ndirty, uint32_t* ref, void* stream);
 void launch_dbg_holders(const Dev& d, uint32_t first, uint32_t n, uint32_t* out, void* stream);  // swim_debug_holders
 
 }  // namespace swim

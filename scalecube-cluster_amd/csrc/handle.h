@@ -59,6 +59,11 @@ struct swim_handle {
   volatile uint32_t* hflag = nullptr; // host-mapped flag word written by k_tick_flag (W == 1)
   unsigned long long* xi_host_h = nullptr;  // host side of Dev::xi_host
   hipEvent_t ev_member = nullptr;
+  // rebasing (step.hip rebase_check): a chunk's baseline is replaced once rb_thr streamed compares of it found no
+  // difference (0: as many as there are rows), looked at no more often than every rb_int ticks (SWIM_CAPS rbt=, rbi=)
+  uint32_t rb_thr = 0, rb_int = swim::REBASE_CHECK;
+  uint64_t next_rebase = 0;  // tick of the next look at the rebase counters (step.hip rebase_check)
+  uint64_t rebases = 0;  // k_rebase runs since create (swim_debug_diff_dirty)
   uint64_t next_scrub = swim::SCRUB;  // tick of the next k_s_scrub (16-bit holder entries, engine.h)
   bool no_skip = getenv("SWIM_NO_GOSSIP_SKIP") != nullptr;  // debugging aid: always run the gossip data plane
   bool no_pipe = getenv("SWIM_NO_PIPELINE") != nullptr;    // debugging aid: no early SYNC diff of the next tick

@@ -77,15 +77,17 @@ __global__ void k_init_rows(Dev d) {
     uint32_t* ra = d.rowa + (size_t)li * d.NS;
     for (uint32_t s = threadIdx.x; s < d.NS; s += blockDim.x) {
       const uint64_t v = s >= d.N ? 0ull : (d.init_mode == 1 || m == s) ? full : 0ull;
-      rk[s] = key32(v);
+      key_put(d, rk, nullptr, li, s, key32(v), 0u);  // (the mask: below, the whole row's at once)
       ra[s] = aux32(v);
-      if (d.rowk8) d.rowk8[(size_t)li * d.NS8 + s] = key8(key32(v));
     }
     if (d.rowk8)  // (the 8-bit plane's wider padding: zero, absent)
       for (uint32_t s = d.NS + threadIdx.x; s < d.NS8; s += blockDim.x) d.rowk8[(size_t)li * d.NS8 + s] = 0;
-    if (d.W > 1)  // dirty chunks against base_row: none for a PRECONVERGED row, the own chunk for a cold join
+    // dirty chunks against the baseline (the PRECONVERGED row, an empty row for a cold join): none for a PRECONVERGED
+    // row, the own chunk for a cold join
+    if (uint64_t* rd = row_dirty(d, li))
       for (uint32_t w = threadIdx.x; w < d.MW; w += blockDim.x)
-        d.rdirty[(size_t)li * d.MW + w] = (d.init_mode != 1 && (m / CH) >> 6 == w) ? 1ull << ((m / CH) & 63) : 0ull;
+        rd[w] = (d.init_mode != 1 && (m / CH) >> 6 == w) ? 1ull << ((m / CH) & 63) : 0ull;
+    if (d.W == 1 && d.MW && threadIdx.x < 3) d.ms[li].cstat[threadIdx.x] = 0;  // (one GPU: the rebase counters)
   }
 }
 
@@ -361,6 +363,12 @@ __device__ __forceinline__ void diff_fetch(const Dev& d, uint32_t b, const uint4
     }
     const uint8_t* r8 = d.rowk8 + lidx(d, D.z) * d.NS8 + n0;
     const uint4 z = make_uint4(0, 0, 0, 0), e = make_uint4(~0u, ~0u, ~0u, ~0u);
+    // one GPU: a chunk of the item that the lister found clean in both rows (equal, row_dirty) is not loaded: its
+    // wave compares zeros and writes the two segments' zero counts
+    if (!SHARDED && !((D.w >> __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) & 1u)) {
+      x[0] = x[1] = x[2] = x[3] = z;
+      return;
+    }
     x[0] = n0 < d.NS8 ? (p8 ? ld_c4((const uint32_t*)p8) : e) : z;
     x[1] = n0 + 16 < d.NS8 ? (p8 ? ld_c4((const uint32_t*)(p8 + 16)) : e) : z;
     x[2] = n0 < d.NS8 ? ld_c4((const uint32_t*)r8) : z;
@@ -493,6 +501,8 @@ __device__ __forceinline__ void diff_wave8(const Dev& d, uint32_t b, const uint4
     return;
   }
   if (dl && __ballot(ab) && lane == 0) atomicOr(&d.msgs[b][mi].kind, KF_ABS);  // (rare: a record the payload lacks)
+  if (!SHARDED && d.MW && lane == 0)  // a streamed chunk that differed (k_rebase's policy)
+    atomicAdd(&d.ms[c + (threadIdx.x >> 6)].cstat[1], 1ull);
   uint32_t incl = nc;
 #pragma unroll
   for (uint32_t o = 1; o < 64; o <<= 1) {
@@ -595,21 +605,23 @@ __device__ __forceinline__ void stream_wide(const Dev& d, uint32_t b, const uint
 template <bool SHARDED>
 __device__ __forceinline__ void stream_narrow(const Dev& d, uint32_t b, const uint4* lst, uint32_t n, uint32_t blk,
                                               uint32_t nblk, const uint4& e0, const uint4& e1) {
-  constexpr uint32_t PER = 4;
-  const uint32_t nit = (d.NCHUNK + PER - 1) / PER, total = n * nit;
+  // a row shard's list has an entry per message (every item of it is streamed); one GPU's an entry per item, its
+  // fourth word item index << 4 | chunks to stream (k_ack_resolve)
+  constexpr uint32_t PER = NPER;
+  const uint32_t nit = SHARDED ? (d.NCHUNK + PER - 1) / PER : 1u, total = n * nit;
   uint4 cur[4], dc = make_uint4(0, 0, 0, 0), dn = e1;
   uint32_t pw;
   bool nr;
   if (blk < total) {
     dc = e0;
-    diff_fetch<SHARDED>(d, b, dc, (blk % nit) * PER, cur, pw, nr, true);
+    diff_fetch<SHARDED>(d, b, dc, (SHARDED ? blk % nit : dc.w >> 4) * PER, cur, pw, nr, true);
   }
   for (uint32_t w = blk; w < total; w += nblk) {
     uint4 nxt[4], dnn = make_uint4(0, 0, 0, 0);
     const uint4 du = uni(dn);
-    if (w + nblk < total) diff_fetch<SHARDED>(d, b, du, ((w + nblk) % nit) * PER, nxt, pw, nr, true);
-    if (w + 2 * nblk < total) dnn = lst[(w + 2 * nblk) / nit];
-    diff_wave8<SHARDED>(d, b, dc, (w % nit) * PER, cur);
+    if (w + nblk < total) diff_fetch<SHARDED>(d, b, du, (SHARDED ? (w + nblk) % nit : du.w >> 4) * PER, nxt, pw, nr, true);
+    if (w + 2 * nblk < total) dnn = lst[SHARDED ? (w + 2 * nblk) / nit : w + 2 * nblk];
+    diff_wave8<SHARDED>(d, b, dc, (SHARDED ? w % nit : dc.w >> 4) * PER, cur);
 #pragma unroll
     for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
     dc = du;
@@ -637,9 +649,10 @@ __global__ void __launch_bounds__(256, DIFF_WAVES) k_sync_diff(const Dev* __rest
   // this block's first two narrow entries, issued before the lengths arrive
   uint4 e0 = make_uint4(0, 0, 0, 0), e1 = e0;
   if (dl) {
-    const uint32_t nit = (d.NCHUNK + 3) / 4, cap = d.MSGCAP - 1;
-    e0 = ((const uint4*)d.dlist)[min(blockIdx.x / nit, cap)];
-    e1 = ((const uint4*)d.dlist)[min((blockIdx.x + gridDim.x) / nit, cap)];
+    // (one GPU: an entry per item, MSGCAP x items per message of them)
+    const uint32_t nit = (d.NCHUNK + NPER - 1) / NPER, cap = (SHARDED ? d.MSGCAP : d.MSGCAP * nit) - 1;
+    e0 = ((const uint4*)d.dlist)[min(SHARDED ? blockIdx.x / nit : blockIdx.x, cap)];
+    e1 = ((const uint4*)d.dlist)[min(SHARDED ? (blockIdx.x + gridDim.x) / nit : blockIdx.x + gridDim.x, cap)];
   }
   const uint32_t nmsg = d.nmsg[b] < d.MSGCAP ? d.nmsg[b] : d.MSGCAP;
   const uint32_t nwide = dl ? *(volatile uint32_t*)d.ndlw : nmsg;
@@ -652,7 +665,7 @@ __global__ void __launch_bounds__(256, DIFF_WAVES) k_sync_diff(const Dev* __rest
       if (timed) atomicAdd(&d.ctr[C_DIFFWIDE], (unsigned long long)nmsg);
     }
   }
-  const uint32_t nblk = gridDim.x, ntot = nnar * ((d.NCHUNK + 3) / 4);
+  const uint32_t nblk = gridDim.x, ntot = SHARDED ? nnar * ((d.NCHUNK + NPER - 1) / NPER) : nnar;
   if (nnar) stream_narrow<SHARDED>(d, b, (const uint4*)d.dlist, nnar, blockIdx.x, nblk, uni(e0), e1);
   stream_wide<SHARDED>(d, b, dl ? (const uint4*)d.dlist_w : nullptr, nwide, (blockIdx.x + nblk - ntot % nblk) % nblk,
                        nblk, scan, base, timed);
@@ -683,7 +696,25 @@ struct ResArgs {
   const uint32_t *mlog, *base_row;
   const uint64_t *rx_mask, *rx_off;
   const uint8_t* xa_recv;
+  // one GPU: the rows' dirty-chunk masks when they are consulted (null: every chunk of a narrow payload is streamed),
+  // whether the skip statistics are kept (one GPU with masks), the members' records (masks, rebase counters) and the
+  // subjects
+  MS* dms;
+  uint32_t dstat;
+  uint32_t N;
+  uint32_t* hflag;  // host-mapped (Dev::hflag): [7] set when a chunk was streamed (the host then looks at the counters)
 };
+
+// one GPU: the chunks of item t (chunks NPER t ...) of a narrow payload src -> dst that k_sync_diff must stream, one bit
+// each: a chunk clean in both rows equals the baseline's in both (row_dirty), so all its compares are decided (equal: no
+// candidate, no absent record) without a load. Without masks: every chunk the payload has.
+__device__ __forceinline__ uint32_t item_need(const ResArgs& d, uint32_t src, uint32_t dst, uint32_t t) {
+  const uint32_t nv = min(NPER, d.NCHUNK - NPER * t), valid = (1u << nv) - 1u;
+  if (!d.dms) return valid;
+  const uint32_t w = (NPER * t) >> 6;  // (64 is a multiple of NPER: an item's bits lie in one word)
+  const uint64_t need = d.dms[src].dirty[w] | d.dms[dst].dirty[w];
+  return (uint32_t)(need >> ((NPER * t) & 63u)) & valid;
+}
 
 // subject v of a message's payload: the sender's live row, its arena snapshot, or (W > 1) a payload received from
 // another shard (the shipped chunk if the chunk mask has it, else the baseline row)
@@ -770,41 +801,88 @@ __device__ __forceinline__ bool res_wave(const ResArgs& d, uint32_t i, uint32_t 
 }
 
 // sharded handles: every message of the tick, one wave each; the unresolved ones go to the list k_sync_diff streams
+// One GPU: an unresolved narrow payload is listed item by item, only the items with a chunk that is dirty in the
+// sender's or in the receiver's row (item_need); the other items' candidate segments get their zero counts here, and a
+// payload without any such chunk is decided here (ncand = 0, no entry: merge_payload reads no chunk_meta then).
 __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint32_t spec, uint32_t timed) {
   if (spec && *(volatile uint32_t*)d.halt) return;
   __shared__ uint32_t sv_[8][64], sc_[8][64];
-  __shared__ uint4 slist[8], wlist[8];
-  __shared__ uint32_t nstream, nwide, nres, sbase, wbase;
+  __shared__ uint4 wlist[8];
+  // per block and round: narrow list entries, wide ones, resolved messages, narrow messages (listed or decided here),
+  // those decided here, their chunks streamed and the subjects of those
+  __shared__ uint32_t nstream, nwide, nres, nnarm, nskipm, nchs, nsubj, sbase, wbase;
+  // chunk compares streamed, per chunk, added up per block (k_rebase's policy; a chunk past SCH: global atomics)
+  constexpr uint32_t SCH = 512;
+  __shared__ uint32_t sch[SCH];
+  if (d.dms) {
+    if (threadIdx.x < SCH) sch[threadIdx.x] = 0;
+    __syncthreads();
+  }
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   volatile uint32_t* sv = sv_[wv];  // this wave's lists (volatile: read across lanes)
   volatile uint32_t* sc = sc_[wv];
   const uint32_t nmsg = min(*d.nmsg, d.MSGCAP);
+  const bool items = d.W == 1;  // the narrow list's form (engine.h NPER)
+  const uint32_t nit = (d.NCHUNK + NPER - 1) / NPER;
   // block-uniform loop, one message per wave; the stream list and the counters take one atomic per block (a few
   // hundred waves adding to one address one by one took ~17 us per tick at C3)
   for (uint32_t base = blockIdx.x * 8; base < nmsg; base += gridDim.x * 8) {
-    if (threadIdx.x == 0) nstream = nwide = nres = 0;
+    if (threadIdx.x == 0) nstream = nwide = nres = nnarm = nskipm = nchs = nsubj = 0;
     __syncthreads();
     const uint32_t i = base + wv;
+    uint32_t woff = 0, wcnt = 0, src = 0, dst = 0, pw = 0;  // this wave's narrow entries: place in the block's, count
     if (i < nmsg) {  // wave-uniform
       if (res_wave(d, i, k, lane, sv, sc)) {
         if (lane == 0) atomicAdd(&nres, 1u);
-      } else if (lane == 0) {  // its entry in the narrow list (one GPU, unpinned live row) or the wide one
+      } else {  // its entries in the narrow list (one GPU, unpinned live row) or its entry in the wide one
         const SyncMsg& mm = d.msgs[i];
-        const uint32_t pw = desc_pay(mm);
-        const uint4 e = make_uint4(i, mm.src, mm.dst, pw);
-        if (d.k8 && (pw == NEVER || (d.W > 1 && pw != DESC_DEFER && (pw & PAY_RX) && !(pw & DESC_PIN))))
-          slist[atomicAdd(&nstream, 1u)] = e;
-        else
-          wlist[atomicAdd(&nwide, 1u)] = e;
+        src = mm.src, dst = mm.dst, pw = desc_pay(mm);
+        if (d.k8 && (pw == NEVER || (d.W > 1 && pw != DESC_DEFER && (pw & PAY_RX) && !(pw & DESC_PIN)))) {
+          uint32_t nc = 0;  // this lane's items' chunks to stream
+          if (items) {
+            for (uint32_t t0 = 0; t0 < nit; t0 += 64) {
+              const uint32_t m4 = t0 + lane < nit ? item_need(d, src, dst, t0 + lane) : 0u;
+              wcnt += (uint32_t)__popcll(__ballot(m4 != 0));
+              nc += __popc(m4);
+              if (d.dms)  // (with masks a streamed chunk is the rare case)
+                for (uint32_t q = m4; q; q &= q - 1) {
+                  const uint32_t c = NPER * (t0 + lane) + (uint32_t)(__ffs(q) - 1);
+                  if (c < SCH) atomicAdd(&sch[c], 1u);
+                  else atomicAdd(&d.dms[c].cstat[0], 1ull);
+                  d.dms[c].cstat[2] = src;  // (any sender of the chunk serves as k_rebase's row)
+                }
+            }
+          } else {
+            wcnt = 1;
+          }
+          if (items && nc) {
+            atomicAdd(&nchs, nc);
+            atomicAdd(&nsubj, nc * CH);
+          }
+          if (lane == 0) {
+            atomicAdd(&nnarm, 1u);
+            if (wcnt) woff = atomicAdd(&nstream, wcnt);
+            else {
+              d.msgs[i].ncand = 0;  // every compare decided: nothing differs
+              atomicAdd(&nskipm, 1u);
+            }
+            // (the last chunk's subjects: up to N)
+            if (items && (item_need(d, src, dst, nit - 1) >> ((d.NCHUNK - 1) % NPER)) & 1u)
+              atomicSub(&nsubj, d.NCHUNK * CH - d.N);
+          }
+          woff = __shfl(woff, 0);
+        } else if (lane == 0) {
+          wlist[atomicAdd(&nwide, 1u)] = make_uint4(i, src, dst, pw);
+        }
       }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
       if (nstream) sbase = atomicAdd(d.ndl, nstream);
       if (nwide) wbase = atomicAdd(d.ndlw, nwide);
-      if (nstream + nwide) {  // the messages k_sync_diff streams (the wide ones: 8 B per subject)
-        atomicAdd(&d.ctr[C_DIFFMSG_ALL], (unsigned long long)(nstream + nwide));
-        if (timed) atomicAdd(&d.ctr[C_DIFFMSG], (unsigned long long)(nstream + nwide));
+      if (nnarm + nwide) {  // the messages k_sync_diff streams (the wide ones: 8 B per subject) or this kernel decided
+        atomicAdd(&d.ctr[C_DIFFMSG_ALL], (unsigned long long)(nnarm + nwide));
+        if (timed) atomicAdd(&d.ctr[C_DIFFMSG], (unsigned long long)(nnarm + nwide));
       }
       if (nwide && d.W > 1) {  // (one GPU: k_sync_diff counts its wide messages)
         atomicAdd(&d.ctr[C_DIFFWIDE_ALL], (unsigned long long)nwide);
@@ -814,11 +892,41 @@ __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint
         atomicAdd(&d.ctr[C_ACKRES_ALL], (unsigned long long)nres);
         if (timed) atomicAdd(&d.ctr[C_ACKRES], (unsigned long long)nres);
       }
+      if (d.dstat && nnarm) {
+        if (nchs) {
+          atomicAdd(&d.ctr[C_DSTREAM], (unsigned long long)nchs);
+          atomicAdd(&d.ctr[C_DSUBJ_ALL], (unsigned long long)nsubj);
+          if (timed) atomicAdd(&d.ctr[C_DSUBJ], (unsigned long long)nsubj);
+        }
+        if (nskipm) atomicAdd(&d.ctr[C_DMSGSKIP], (unsigned long long)nskipm);
+        if (nchs && d.dms) *(volatile uint32_t*)(d.hflag + 7) = 1u;
+      }
     }
     __syncthreads();
-    if (threadIdx.x < nstream) ((uint4*)d.dlist)[sbase + threadIdx.x] = slist[threadIdx.x];
+    if (d.dms && nchs)  // (block-uniform)
+      for (uint32_t c = threadIdx.x; c < min(d.NCHUNK, SCH); c += blockDim.x)
+        if (const uint32_t v = sch[c]) {
+          atomicAdd(&d.dms[c].cstat[0], (unsigned long long)v);
+          sch[c] = 0;
+        }
+    if (wcnt && !items) {
+      if (lane == 0) ((uint4*)d.dlist)[sbase + woff] = make_uint4(i, src, dst, pw);
+    } else if (wcnt) {
+      uint32_t o = sbase + woff;
+      for (uint32_t t0 = 0; t0 < nit; t0 += 64) {
+        const uint32_t t = t0 + lane, m4 = t < nit ? item_need(d, src, dst, t) : 0u;
+        const unsigned long long em = __ballot(m4 != 0);
+        if (m4) ((uint4*)d.dlist)[o + (uint32_t)__popcll(em & ((1ull << lane) - 1ull))] = make_uint4(i, src, dst, t << 4 | m4);
+        o += (uint32_t)__popcll(em);
+        if (t < nit && !m4)  // an item without a chunk to stream: its segments' zero counts (merge_payload's chunk walk)
+          for (uint32_t g = 2 * NPER * t; g < min(2 * NPER * (t + 1), d.NMETA); ++g) {
+            uint32_t* cm = d.chunk_meta + ((size_t)i * d.NMETA + g) * 2;
+            cm[0] = cm[1] = 0;
+          }
+      }
+    }
     if (threadIdx.x >= 64 && threadIdx.x - 64 < nwide) ((uint4*)d.dlist_w)[wbase + threadIdx.x - 64] = wlist[threadIdx.x - 64];
-    __syncthreads();  // (slist and the counts are reused)
+    __syncthreads();  // (wlist and the counts are reused)
   }
 }
 
@@ -878,6 +986,72 @@ __global__ void __launch_bounds__(256) k_hash(Dev d, uint64_t* out, uint32_t now
 
 __global__ void k_tick_end(Dev d, uint32_t k) { tick_end(d, k); }
 
+// one GPU, between steps: a host write of one key (swim_debug_set_incarnation)
+__global__ void k_key_set(Dev d, uint32_t m, uint32_t s, uint32_t key) {
+  uint32_t* rk = d.rowk + (size_t)m * d.NS;
+  key_put(d, rk, row_dirty(d, m), m, s, key, rk[s]);
+}
+void launch_key_set(const Dev& d, uint32_t m, uint32_t s, uint32_t key, void* stream) {
+  hipLaunchKernelGGL(k_key_set, dim3(1), dim3(1), 0, (hipStream_t)stream, d, m, s, key);
+}
+
+// one GPU, between ticks: chunk c of row r becomes chunk c of the baseline. Every row's bit c is recomputed against it
+// (set iff the row's chunk differs from row r's: exact for any r, which only decides how many rows come out clean).
+// The baseline is not stored: it is what the clean rows hold. The chunk's policy counters start again. One block per
+// row, grid-strided.
+__global__ void __launch_bounds__(256) k_rebase(Dev d, uint32_t c, uint32_t r) {
+  const uint32_t s0 = c * CH, s1 = min((c + 1) * CH, d.NS);
+  const uint32_t* rr = d.rowk + (size_t)r * d.NS;
+  for (uint32_t li = blockIdx.x; li < d.NL; li += gridDim.x) {
+    const uint32_t* rk = d.rowk + (size_t)li * d.NS;
+    bool diff = false;
+    for (uint32_t s = s0 + threadIdx.x; s < s1; s += blockDim.x) diff |= rk[s] != rr[s];
+    diff = __syncthreads_or(diff);
+    if (threadIdx.x == 0) {
+      uint64_t* w = row_dirty(d, li) + (c >> 6);
+      const uint64_t bit = 1ull << (c & 63);
+      *w = diff ? *w | bit : *w & ~bit;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) d.ms[c].cstat[0] = d.ms[c].cstat[1] = 0;
+}
+void launch_rebase(const Dev& d, uint32_t c, uint32_t r, void* stream) {
+  hipLaunchKernelGGL(k_rebase, dim3(min(d.NL, 4096u)), dim3(256), 0, (hipStream_t)stream, d, c, r);
+}
+
+// one GPU: the dirty masks' invariant, tested directly: all the rows whose bit c is clear hold the same chunk c (keys,
+// and their 8-bit shadows): the baseline's. k_dirty_ref finds, per chunk, the first such row; k_dirty_check compares
+// every other one with it, one block per (row, chunk), grid-strided, and counts the dirty pairs.
+__global__ void k_dirty_ref(Dev d, uint32_t* ref) {
+  const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
+  if (li >= d.NL) return;
+  const uint64_t* rd = row_dirty(d, li);
+  for (uint32_t c = 0; c < d.NCHUNK; ++c)
+    if (!((rd[c >> 6] >> (c & 63)) & 1ull)) atomicMin(&ref[c], li);
+}
+__global__ void __launch_bounds__(256) k_dirty_check(Dev d, uint32_t* viol, uint32_t* ndirty, const uint32_t* ref) {
+  const uint64_t total = (uint64_t)d.NL * d.NCHUNK;
+  for (uint64_t w = blockIdx.x; w < total; w += gridDim.x) {
+    const uint32_t li = (uint32_t)(w / d.NCHUNK), c = (uint32_t)(w % d.NCHUNK);
+    if ((row_dirty(d, li)[c >> 6] >> (c & 63)) & 1ull) {
+      if (threadIdx.x == 0) atomicAdd(ndirty, 1u);
+      continue;
+    }
+    const size_t r = ref[c];  // (a clean row exists: this one)
+    bool bad = false;
+    for (uint32_t s = c * CH + threadIdx.x; s < min((c + 1) * CH, d.NS); s += blockDim.x) {
+      bad |= d.rowk[(size_t)li * d.NS + s] != d.rowk[r * d.NS + s];
+      if (d.rowk8) bad |= d.rowk8[(size_t)li * d.NS8 + s] != key8(d.rowk[r * d.NS + s]);
+    }
+    if (__syncthreads_or(bad) && threadIdx.x == 0) atomicAdd(viol, 1u);
+  }
+}
+void launch_dirty_check(const Dev& d, uint32_t* viol, uint32_t* ndirty, uint32_t* ref, void* stream) {
+  hipMemsetAsync(ref, 0xFF, 4ull * d.NCHUNK, (hipStream_t)stream);
+  hipLaunchKernelGGL(k_dirty_ref, dim3((d.NL + 255) / 256), dim3(256), 0, (hipStream_t)stream, d, ref);
+  hipLaunchKernelGGL(k_dirty_check, dim3(4096), dim3(256), 0, (hipStream_t)stream, d, viol, ndirty, ref);
+}
+
 // slot sharding: the all-reduced gossip-count deltas of this tick
 __global__ void k_held_add(Dev d, const int32_t* sum) {
   const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -928,7 +1102,7 @@ void launch_init(const Dev& d, void* stream) {
   hipLaunchKernelGGL(k_init_rows, dim3(4096), dim3(256), 0, st, d);
   hipLaunchKernelGGL(k_init_lists, dim3(4096), dim3(256), 0, st, d);
   hipLaunchKernelGGL(k_init_slots, dim3(cdiv(d.SLOTS, 256)), dim3(256), 0, st, d);
-  if (d.W > 1) hipLaunchKernelGGL(k_init_base, dim3(cdiv(d.NS8, 256)), dim3(256), 0, st, d);
+  if (d.base_row) hipLaunchKernelGGL(k_init_base, dim3(cdiv(d.NS8, 256)), dim3(256), 0, st, d);
 }
 
 // timed: this launch is bracketed by profiling events; it adds its message count to ctr[C_DIFFMSG]
@@ -970,7 +1144,8 @@ static void launch_ack_resolve(const Dev& d, uint32_t k, hipStream_t st, bool sp
   const uint32_t b = (k - 1) & 1;
   const ResArgs ra{d.halt, d.nmsg + b, d.tl_tick, d.tl_n, d.tlog, d.rowk, d.arena[b], d.msgs[b], d.dlist, d.ndl,
                    d.dlist_w, d.ndlw, d.chunk_meta, d.pool_used, d.err, d.pool, d.ctr, d.NL, d.NS, d.MSGCAP, d.NCHUNK, d.POOLCAP, d.NMETA,
-                   d.rowk8 ? 1u : 0u, d.lo, d.W, d.MW, d.mlog, d.base_row, d.rx_mask, d.rx_off, d.xa_recv};
+                   d.rowk8 ? 1u : 0u, d.lo, d.W, d.MW, d.mlog, d.base_row, d.rx_mask, d.rx_off, d.xa_recv,
+                   (d.ackres & ACKRES_DIRTY) ? d.ms : nullptr, d.W == 1 && d.MW ? 1u : 0u, d.N, d.hflag};
   hipLaunchKernelGGL(k_ack_resolve, dim3(128), dim3(512), 0, st, ra, k, spec ? 1u : 0u, timed ? 1u : 0u);
 }
 

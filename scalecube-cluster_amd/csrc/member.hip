@@ -26,7 +26,7 @@ struct ML {
   int32_t pingIdx, remoteIdx;
   uint64_t evHash;
   uint32_t *rk, *ra;  // this observer's row: key plane and aux plane (swim_common.h)
-  uint64_t* rd;       // W > 1: its dirty-chunk mask against base_row (Dev::rdirty), else null
+  uint64_t* rd;       // its dirty-chunk mask (row_dirty); null when none is kept
   uint32_t *fdl, *gl, *subs, *paths, *fetch, *groups;
   uint32_t c[8];  // this tick's op counters (one member, one tick: u32; summed per wave in u64)
   uint32_t pend;  // this tick's SYNC messages that carry the live row: a chain through SyncMsg.pad (NEVER = none)
@@ -114,7 +114,7 @@ __device__ __forceinline__ void copy_row_to(ML& L, uint32_t r) {
   uint4* dst4 = (uint4*)(d.arena[b] + (size_t)r * d.NS);
 #pragma unroll 16
   for (uint32_t s = 0; s < d.NS / 4; ++s) dst4[s] = src4[s];
-  if (L.rd)
+  if (d.W > 1)
     for (uint32_t w = 0; w < d.MW; ++w) d.arena_dirty[b][(size_t)r * d.MW + w] = L.rd[w];
 }
 
@@ -188,9 +188,7 @@ __device__ __forceinline__ void row_put(ML& L, uint32_t s, uint64_t v, uint32_t 
     }
   }
   if (L.d->ackres && old != k) tl_add(L, s);
-  L.rk[s] = k;
-  if (L.d->rowk8) L.d->rowk8[lidx(*L.d, L.m) * L.d->NS8 + s] = key8(k);
-  if (L.rd && k != L.d->base_row[s]) L.rd[(s / CH) >> 6] |= 1ull << ((s / CH) & 63);
+  key_put(*L.d, L.rk, L.rd, lidx(*L.d, L.m), s, k, old);
   L.ra[s] = aux32(v);
 }
 __device__ __forceinline__ void row_put(ML& L, uint32_t s, uint64_t v) { row_put(L, s, v, L.rk[s]); }
@@ -1115,7 +1113,7 @@ __device__ __forceinline__ void ml_init(ML& L, const Dev& d, uint32_t m, uint32_
   const size_t li = lidx(d, m);  // per-observer arrays hold only this shard's rows
   L.rk = d.rowk + li * d.NS;
   L.ra = d.rowa + li * d.NS;
-  L.rd = d.W > 1 ? d.rdirty + li * d.MW : nullptr;
+  L.rd = row_dirty(d, li);
   L.fdl = d.fdl + li * d.LCAP;
   L.gl = d.gl + li * d.LCAP;
   L.subs = d.subs + li * SUBCAP * 4;
@@ -1809,10 +1807,10 @@ __device__ __forceinline__ void inbox_batch(ML& L, uint32_t lane, uint32_t cnt, 
   if (acc && !acc_later) {  // the subject's last accepted record is what the row holds after the batch
     uint64_t v = (v0 & ~KEY_MASK) | rec_key(s1, i1);
     v = rec_with_timer(v, s1 == ST_SUSPECT ? ((alive_before || T0 == 0) ? dl : T0) : 0u);
-    L.rk[s] = key32(v);
+    key_put(d, L.rk, L.rd, lidx(d, L.m), s, key32(v), k0, false);
     L.ra[s] = aux32(v);
-    if (d.rowk8) d.rowk8[lidx(d, L.m) * d.NS8 + s] = key8(key32(v));
   }
+  dirty_mark_wave(L.rd, acc && !acc_later, s);  // (an accepted key is above the row's: every one is a change)
   if (act) L.c[C_R]++;
   if (acc) L.c[C_W]++;
   if (d.ackres) {  // tl_add of each accepted write, in order

@@ -1,6 +1,7 @@
 // step.hip — swim_step: the tick loop and its four paths (one GPU: a tick, a speculative batch; row shards: a
 // speculative batch, a tick). The order of launches, event records, host waits and grow_caps calls on each path is
 // what the results and the timed path depend on; the dumps and the profile bookkeeping are in diag.hip.
+#include <cstddef>
 #include "handle.h"
 
 #include <algorithm>
@@ -192,6 +193,30 @@ int shard_tick(swim_handle* h, Step& s) {
 
 }  // namespace
 
+// One GPU with dirty-chunk skipping: the baseline follows the cluster. The lister counts, per chunk,
+// the compares it had streamed because the chunk was dirty, the diff those that found a difference; once the wasted
+// ones (streamed without a difference) since the chunk's last rebase reach the number of rows, the chunk's baseline
+// becomes some sender's chunk (k_rebase: one pass over the chunk of every row, about what those compares cost), and
+// the rows that agree with it are clean again. Called between ticks, where the host holds no queued member launch; the
+// counters are read back only when the lister flagged a streamed chunk (never in a cluster whose rows are all clean).
+static int rebase_check(swim_handle* h) {
+  const Dev& d = h->d;
+  if (h->tick < h->next_rebase || !h->hflag[7]) return SWIM_OK;
+  h->next_rebase = h->tick + h->rb_int;
+  h->hflag[7] = 0;
+  std::vector<unsigned long long> c(3ull * d.NCHUNK);  // chunk q's streamed, differed, sender: member q's record
+  HIPCK(hipMemcpy2DAsync(c.data(), 24, (const char*)d.ms + offsetof(MS, cstat), sizeof(MS), 24, d.NCHUNK, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  const unsigned long long thr = h->rb_thr ? h->rb_thr : d.NL;
+  for (uint32_t q = 0; q < d.NCHUNK; ++q) {
+    const unsigned long long st = c[3ull * q], df = c[3ull * q + 1], r = c[3ull * q + 2];
+    if (st < df + thr || r >= d.NL) continue;
+    launch_rebase(d, q, (uint32_t)r, h->stream);
+    h->rebases++;
+  }
+  return SWIM_OK;
+}
+
 extern "C" int swim_step(swim_handle* h, uint32_t n) {
   if (!h) return SWIM_EINVAL;
   if (h->grp) return group_step(h, n);
@@ -210,6 +235,7 @@ extern "C" int swim_step(swim_handle* h, uint32_t n) {
       h->next_scrub = h->tick + SCRUB;
     }
     s.nb = (uint32_t)std::min<uint64_t>(n, s.i + (h->next_scrub - h->tick));
+    if ((d.ackres & ACKRES_DIRTY) && d.W == 1 && (rc = rebase_check(h)) != SWIM_OK) return rc;
     // P0 gossip creations before the member kernel: RUMOR-mode churn rumors, then the user gossips queued by the host
     if (d.churn && k % d.ping_t == 0) launch_churn(d, k, h->stream);
     if (s.i == 0 && !h->ugq.empty() && (rc = upload_user_gossips(h, k)) != SWIM_OK) return rc;

@@ -210,7 +210,10 @@ DEBUG_SIGNATURES = {
     "swim_debug_caps": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
     "swim_debug_holders": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "swim_debug_set_incarnation": (C.c_int, [_H, C.c_uint32, C.c_uint32]),
+    "swim_debug_diff_dirty": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
+    "swim_debug_dirty_check": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
 }
+DD_NAMES = ["skipped", "streamed", "msg_skipped", "rebases", "dirty_rows"]
 CAP_NAMES = ["slots", "ring", "receipts", "replay", "history", "growths"]
 
 
@@ -243,6 +246,30 @@ def debug_set_incarnation(lib, handle, m, inc):
     fn = lib.swim_debug_set_incarnation
     fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_set_incarnation"]
     return fn(handle, m, inc)
+
+
+def debug_diff_dirty(lib, handle, n=len(DD_NAMES)):
+    """{name: count} of the SYNC diff's dirty-chunk skipping since create (include/swimhip_debug.h
+    swim_debug_diff_dirty); n = 4 leaves out dirty_rows, which costs a pass over the key plane."""
+    fn = lib.swim_debug_diff_dirty
+    fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_diff_dirty"]
+    out = (C.c_uint64 * len(DD_NAMES))()
+    rc = fn(handle, out, n)
+    if rc != 0:
+        raise RuntimeError(f"swim_debug_diff_dirty rc={rc}")
+    return dict(zip(DD_NAMES[:n], (int(x) for x in out)))
+
+
+def debug_dirty_check(lib, handle):
+    """Clean (row, chunk) pairs that differ from the baseline (the first clean row of the chunk): 0 in a correct engine
+    (swim_debug_dirty_check)."""
+    fn = lib.swim_debug_dirty_check
+    fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_dirty_check"]
+    v = C.c_uint64(0)
+    rc = fn(handle, C.byref(v))
+    if rc != 0:
+        raise RuntimeError(f"swim_debug_dirty_check rc={rc}")
+    return int(v.value)
 
 
 def debug_fallbacks(lib, handle):
