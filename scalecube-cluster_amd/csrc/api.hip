@@ -831,8 +831,11 @@ int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n) {
   uint64_t dirty = 0;
   int rc;
   if (n > SWIM_DD_DIRTY_ROWS && (rc = dirty_check(h, &viol, &dirty)) != SWIM_OK) return rc;
-  const uint64_t v[5] = {narrow * d.NCHUNK - c[C_DSTREAM], c[C_DSTREAM], c[C_DMSGSKIP], h->rebases, dirty};
-  for (size_t i = 0; i < n; ++i) out[i] = i < 5 ? v[i] : 0;
+  unsigned long long pindec = 0;
+  HIPCK(hipMemcpy(&pindec, d.ctr_sh + SH_PINDEC, 8, hipMemcpyDeviceToHost));
+  const uint64_t v[8] = {narrow * d.NCHUNK - c[C_DSTREAM], c[C_DSTREAM], c[C_DMSGSKIP], h->rebases, dirty,
+                         pindec,         h->diff_elided, h->diff_halts};
+  for (size_t i = 0; i < n; ++i) out[i] = v[i];
   return SWIM_OK;
 }
 

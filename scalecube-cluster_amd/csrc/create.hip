@@ -406,7 +406,7 @@ static int init_state(swim_handle* h) {
   Dev& d = h->d;
   const uint64_t N = d.N;
   int rc;
-  d.halt = d.mdone + 1;
+  d.halt = (uint32_t*)(d.ctr_sh + SH_HALT);  // (spare words of counter row 0, engine.h)
   if (d.EMAX) {
     std::vector<uint32_t> fl(d.DSCAP);
     for (uint32_t i = 0; i < d.DSCAP; ++i) fl[i] = i;

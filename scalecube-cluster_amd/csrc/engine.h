@@ -90,6 +90,10 @@ constexpr uint32_t XINL = 16384;  // RCCL: bytes per peer moved by the fixed-siz
 // counters (swim_counters order after .tick)
 // 8..12: SWIM_EXP & 4 (and 16..19: the gossip plane's work units per tick, for algorithmic bytes; tools/pmc_gossip.py)
 constexpr uint32_t CSH = 64, CSTRIDE = 64;  // Dev::ctr_sh rows, 512 B apart
+// a row holds 8 counters; row 0's spare words (never summed, zero at create) hold, each on a 128-B line of its own away
+// from the counters' atomics: the three halt words of the speculative batches (Dev::halt), and the pinned live-row
+// payloads the lister decided from the masks (kernels.hip pin_clean; among C_DMSGSKIP). No allocation of their own.
+constexpr uint32_t SH_HALT = 16, SH_PINDEC = 32;
 enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29,
            // dirty-chunk skipping of the SYNC diff (one GPU): narrow 2048-subject chunks the lister had
            // streamed, their subjects over the timed and over all launches (2 B each in swim_counters.diff_key_bytes*),
@@ -328,8 +332,12 @@ struct Dev {
   uint32_t* next_evt; // [N] earliest tick at which a pending path / subscription / fetch needs the member
   uint32_t* mdone;  // finished k_member_tick blocks this tick (the last one runs the end-of-tick resets)
   // speculative batches (W == 1, gossip plane idle): tick + 1 of the member kernel after which the gossip plane was
-  // needed (0: none); every later k_sync_diff / k_member_tick launch of the batch returns at once
-  uint32_t* halt;
+  // needed (0: none); every later k_sync_diff / k_member_tick launch of the batch returns at once.
+  // halt[1], one GPU, batches that queue no k_sync_diff on untimed ticks (step.hip): the diff-halt, tick + 1 of the
+  // lister that listed work for a diff nobody queued (k_ack_resolve); every later launch of the batch returns at once,
+  // member(tick) included, and the host runs that diff. A word of its own: halt[0] = k may also be member(k - 1)'s.
+  // halt[2]: entries the lister has listed since create (the host's re-enable rule)
+  uint32_t* halt;  // [3], adjacent (one copy reads them): ctr_sh + SH_HALT
   uint32_t* trk;    // [NL][TRKL] per receiver: subjects its row changed earlier in this tick's P1 (member.hip)
   unsigned long long* tbm;  // [NL][NW] the same subjects as a bitmap (zero between ticks): merged in subject order
   uint32_t NW;       // u64 words per bitmap row ((N + 63) / 64; no SYNC with implicit views: 0)
@@ -377,7 +385,8 @@ struct Dev {
                             // [1] the halt tick read back after a speculative batch; with rfill: the previous gossip
                             // plane's largest receipt-ring fill [2], routed receipts [3], replay and slow-path sends
                             // [4], [5], history entries in use [6]; [7] a narrow chunk was streamed since the
-                            // host's last look at the rebase counters (k_ack_resolve)
+                            // host's last look at the rebase counters (k_ack_resolve); [8..10] Dev::halt's three
+                            // words read back after a one-GPU speculative batch
   uint32_t* hsh;            // [8] device copy of what hflag holds (tick_flag writes host memory only on a change):
                             // hsh[0] mirrors hflag[0], hsh[1..5] mirror hflag[2..6]
   uint32_t* rfill;          // [1] W == 1: largest ring fill (rtail - rhead) after this tick's receipts (grow_caps)
@@ -443,6 +452,11 @@ struct Dev {
 };
 
 constexpr uint32_t ACKRES_ON = 1, ACKRES_DIRTY = 2;
+// one GPU with the dirty masks consulted and the 8-bit plane: the lister decides pinned live-row payloads from the
+// masks, and a speculative batch may queue no k_sync_diff on its untimed ticks (step.hip)
+__host__ __device__ __forceinline__ bool diff_elidable(const Dev& d) {
+  return d.W == 1 && (d.ackres & ACKRES_DIRTY) && d.rowk8 != nullptr;
+}
 // the dirty-chunk mask of the row at local index li (MW words), or null when none is kept
 __host__ __device__ __forceinline__ uint64_t* row_dirty(const Dev& d, size_t li) {
   if (!d.MW) return nullptr;
@@ -492,7 +506,11 @@ void launch_init(const Dev& d, void* stream);
 // single GPU, per tick k: launch_diff(k) (k > 0), launch_member(k) (+ host flag), then launch_gossip(k) if the flag
 // says a gossip slot is in use; launch_diff(k+1) may be queued before launch_gossip(k)
 // spec: a launch of a speculative batch (it returns at once once d.halt is set)
-void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, bool spec = false);
+// nodiff (one GPU with dirty masks and the 8-bit plane; else ignored): only the lister is queued, told that no
+// k_sync_diff follows it; launch_diff_listed is that diff alone, for the host after a diff-halt (not speculative)
+void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, bool spec = false,
+                 bool nodiff = false);
+void launch_diff_listed(const Dev& d, uint32_t k, void* stream);
 // split: the previous tick ran the gossip plane (routed receipts for P4: k_member_tick parks the members with many,
 // k_inbox_apply runs their P4, a second k_member_tick launch their P5 and P6)
 void launch_member(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, bool spec = false,

@@ -68,6 +68,13 @@ struct swim_handle {
   bool no_skip = getenv("SWIM_NO_GOSSIP_SKIP") != nullptr;  // debugging aid: always run the gossip data plane
   bool no_pipe = getenv("SWIM_NO_PIPELINE") != nullptr;    // debugging aid: no early SYNC diff of the next tick
   bool no_spec = getenv("SWIM_NO_SPECULATION") != nullptr;  // debugging aid: a host wait after every member kernel
+  // one GPU (engine.h diff_elidable): speculative batches queue no k_sync_diff on untimed ticks while elide_on
+  // (step.hip spec_batch); SWIM_NO_ELIDE keeps a diff launch on every tick (measurements, the tests' reference path)
+  bool no_elide = getenv("SWIM_NO_ELIDE") != nullptr;
+  bool elide_on = true;       // off after a diff-halt or a gossip plane, on again after a batch that listed nothing
+  uint32_t listed_seen = 0;   // Dev::halt[2] as last read
+  uint64_t diff_elided = 0;   // ticks run without a k_sync_diff launch (swim_debug_diff_dirty)
+  uint64_t diff_halts = 0;    // batches stopped by a diff-halt
   bool gossip_idle = false;  // W == 1: no gossip slot was in use after the latest member kernel
   bool gossip_ran = false;   // W == 1: the latest tick ran the gossip plane (the next P4 may have routed receipts)
   uint64_t growths = 0;      // capacity growth steps so far (grow_caps)

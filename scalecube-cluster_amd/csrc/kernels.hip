@@ -637,7 +637,9 @@ constexpr uint32_t DIFF_WAVES = 7;
 template <bool SHARDED>
 __global__ void __launch_bounds__(256, DIFF_WAVES) k_sync_diff(const Dev* __restrict__ dp, uint32_t b, uint32_t timed, uint32_t spec) {
   const Dev& d = *dp;  // global, not kernarg (as k_member_tick): a by-value Dev of this size was copied to scratch
-  if (spec && *(volatile uint32_t*)d.halt) return;  // a speculative batch halted at an earlier tick
+  // a speculative batch halted at an earlier tick (either word: this tick's lister raises no diff-halt when its diff
+  // is queued)
+  if (spec && (*(volatile uint32_t*)d.halt | *(volatile uint32_t*)(d.halt + 1))) return;
   __shared__ uint32_t scan[256];
   __shared__ uint32_t base;
   // (timed launches are bracketed by HIP events on the stream. A self-timing variant, first block start to last block
@@ -683,7 +685,8 @@ __global__ void __launch_bounds__(256, DIFF_WAVES) k_sync_diff(const Dev* __rest
 // the fields k_ack_resolve reads, passed as kernel arguments: through Dev* every one of them was a dependent load of
 // its own before the loads that use it (the kernel is a chain of short dependent loads)
 struct ResArgs {
-  const uint32_t *halt, *nmsg, *tl_tick, *tl_n, *tlog, *rowk, *arena;
+  uint32_t* halt;  // Dev::halt: [0] gossip halt, [1] diff-halt, [2] entries listed
+  const uint32_t *nmsg, *tl_tick, *tl_n, *tlog, *rowk, *arena;
   SyncMsg* msgs;
   uint32_t *dlist, *ndl, *dlist_w, *ndlw, *chunk_meta, *pool_used, *err;
   uint64_t* pool;
@@ -703,6 +706,10 @@ struct ResArgs {
   uint32_t dstat;
   uint32_t N;
   uint32_t* hflag;  // host-mapped (Dev::hflag): [7] set when a chunk was streamed (the host then looks at the counters)
+  // one GPU with masks consulted and the 8-bit plane: this buffer's inbound lists (Dev::m_head, m_next), walked for
+  // the pinned live-row payloads (pin_clean); null otherwise (they go to the wide list)
+  const uint32_t *m_head, *m_next;
+  unsigned long long* pindec;  // the count of those decided (engine.h SH_PINDEC)
 };
 
 // one GPU: the chunks of item t (chunks NPER t ...) of a narrow payload src -> dst that k_sync_diff must stream, one bit
@@ -714,6 +721,30 @@ __device__ __forceinline__ uint32_t item_need(const ResArgs& d, uint32_t src, ui
   const uint32_t w = (NPER * t) >> 6;  // (64 is a multiple of NPER: an item's bits lie in one word)
   const uint64_t need = d.dms[src].dirty[w] | d.dms[dst].dirty[w];
   return (uint32_t)(need >> ((NPER * t) & 63u)) & valid;
+}
+
+// one GPU: a pinned live-row payload (message i, one of several payloads of receiver dst in this tick: pin_msg) is
+// decided from the masks when every payload of the receiver's inbound list is a live row and the receiver's row and
+// every one of those senders' rows are clean in every chunk: all those rows equal the baseline, so no payload of the
+// list has a candidate or lacks a record, the receiver's P1 merges nothing and tracks no subject, and no later payload
+// of the list is ever read (merge_payload, payload_key_at): the pinned copy is not needed either. Every message of the
+// list gets the same verdict from the same list. At most PINWALK entries are walked (a longer list, a snapshot or a
+// delayed sibling, any dirty bit: false, the payload is streamed wide as before). Wave-uniform.
+constexpr uint32_t PINWALK = 8;
+__device__ __forceinline__ bool pin_clean(const ResArgs& d, uint32_t i, uint32_t dst, uint32_t lane) {
+  uint64_t any = lane < d.MW ? d.dms[dst].dirty[lane] : 0ull;
+  bool ok = true, found = false;
+  uint32_t q = d.m_head[dst];
+  for (uint32_t n = 0; q != NEVER && n < PINWALK; ++n) {
+    if (q >= d.MSGCAP) return false;
+    const SyncMsg& sm = d.msgs[q];
+    const uint32_t nx = d.m_next[q], pay = sm.payload, kind = sm.kind, ssrc = sm.src;
+    ok &= pay == NEVER && !(kind & KF_DEFER) && ssrc < d.NL;
+    found |= q == i;
+    if (ok && lane < d.MW) any |= d.dms[ssrc].dirty[lane];
+    q = nx;
+  }
+  return ok && found && q == NEVER && !__ballot(any != 0ull);
 }
 
 // subject v of a message's payload: the sender's live row, its arena snapshot, or (W > 1) a payload received from
@@ -804,13 +835,21 @@ __device__ __forceinline__ bool res_wave(const ResArgs& d, uint32_t i, uint32_t 
 // One GPU: an unresolved narrow payload is listed item by item, only the items with a chunk that is dirty in the
 // sender's or in the receiver's row (item_need); the other items' candidate segments get their zero counts here, and a
 // payload without any such chunk is decided here (ncand = 0, no entry: merge_payload reads no chunk_meta then).
+// spec: 1 = a launch of a speculative batch; | 2 = no k_sync_diff follows this launch (one GPU, an untimed tick of a
+// batch that elides the diff, step.hip): a block that lists an entry raises the diff-halt of its tick, halt[1] = k + 1,
+// after which every later launch of the batch returns at once and the host runs diff(k) itself. The blocks of this
+// launch go on whatever their own tick's diff-halt says (the list must be complete); nothing waits on the device.
 __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint32_t spec, uint32_t timed) {
-  if (spec && *(volatile uint32_t*)d.halt) return;
+  if (spec) {
+    const uint32_t hg = *(volatile uint32_t*)d.halt, hd = *(volatile uint32_t*)(d.halt + 1);
+    if (hg || (hd && hd != k + 1u)) return;
+  }
   __shared__ uint32_t sv_[8][64], sc_[8][64];
   __shared__ uint4 wlist[8];
   // per block and round: narrow list entries, wide ones, resolved messages, narrow messages (listed or decided here),
   // those decided here, their chunks streamed and the subjects of those
-  __shared__ uint32_t nstream, nwide, nres, nnarm, nskipm, nchs, nsubj, sbase, wbase;
+  // (npind: pinned live-row payloads decided from the masks, counted with the narrow ones decided here)
+  __shared__ uint32_t nstream, nwide, nres, nnarm, nskipm, nchs, nsubj, sbase, wbase, npind;
   // chunk compares streamed, per chunk, added up per block (k_rebase's policy; a chunk past SCH: global atomics)
   constexpr uint32_t SCH = 512;
   __shared__ uint32_t sch[SCH];
@@ -827,7 +866,7 @@ __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint
   // block-uniform loop, one message per wave; the stream list and the counters take one atomic per block (a few
   // hundred waves adding to one address one by one took ~17 us per tick at C3)
   for (uint32_t base = blockIdx.x * 8; base < nmsg; base += gridDim.x * 8) {
-    if (threadIdx.x == 0) nstream = nwide = nres = nnarm = nskipm = nchs = nsubj = 0;
+    if (threadIdx.x == 0) nstream = nwide = nres = nnarm = nskipm = nchs = nsubj = npind = 0;
     __syncthreads();
     const uint32_t i = base + wv;
     uint32_t woff = 0, wcnt = 0, src = 0, dst = 0, pw = 0;  // this wave's narrow entries: place in the block's, count
@@ -837,7 +876,15 @@ __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint
       } else {  // its entries in the narrow list (one GPU, unpinned live row) or its entry in the wide one
         const SyncMsg& mm = d.msgs[i];
         src = mm.src, dst = mm.dst, pw = desc_pay(mm);
-        if (d.k8 && (pw == NEVER || (d.W > 1 && pw != DESC_DEFER && (pw & PAY_RX) && !(pw & DESC_PIN)))) {
+        if (d.m_head && mm.payload == NEVER && pw != NEVER && pw != DESC_DEFER && pin_clean(d, i, dst, lane)) {
+          if (lane == 0) {  // decided: no entry, no pinned copy; a read of it would raise E_PIN (payload_key_at)
+            d.msgs[i].ncand = 0;
+            d.msgs[i].pin = NEVER;
+            atomicAdd(&nnarm, 1u);
+            atomicAdd(&nskipm, 1u);
+            atomicAdd(&npind, 1u);
+          }
+        } else if (d.k8 && (pw == NEVER || (d.W > 1 && pw != DESC_DEFER && (pw & PAY_RX) && !(pw & DESC_PIN)))) {
           uint32_t nc = 0;  // this lane's items' chunks to stream
           if (items) {
             for (uint32_t t0 = 0; t0 < nit; t0 += 64) {
@@ -880,6 +927,10 @@ __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint
     if (threadIdx.x == 0) {
       if (nstream) sbase = atomicAdd(d.ndl, nstream);
       if (nwide) wbase = atomicAdd(d.ndlw, nwide);
+      if (d.m_head && nstream + nwide) {  // work for k_sync_diff: counted for the host, and a halt if none is queued
+        atomicAdd(d.halt + 2, nstream + nwide);
+        if (spec & 2u) *(volatile uint32_t*)(d.halt + 1) = k + 1u;
+      }
       if (nnarm + nwide) {  // the messages k_sync_diff streams (the wide ones: 8 B per subject) or this kernel decided
         atomicAdd(&d.ctr[C_DIFFMSG_ALL], (unsigned long long)(nnarm + nwide));
         if (timed) atomicAdd(&d.ctr[C_DIFFMSG], (unsigned long long)(nnarm + nwide));
@@ -899,6 +950,7 @@ __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint
           if (timed) atomicAdd(&d.ctr[C_DSUBJ], (unsigned long long)nsubj);
         }
         if (nskipm) atomicAdd(&d.ctr[C_DMSGSKIP], (unsigned long long)nskipm);
+        if (npind) atomicAdd(d.pindec, (unsigned long long)npind);
         if (nchs && d.dms) *(volatile uint32_t*)(d.hflag + 7) = 1u;
       }
     }
@@ -1139,20 +1191,29 @@ static void launch_sync_diff(const Dev& d, uint32_t b, hipStream_t st, uint32_t 
 // single GPU: the tick is cut in three so that the host can hold back the gossip data plane when no slot is in
 // use; the SYNC diff of tick k+1 does not depend on the gossip plane of tick k and is queued in between
 // SYNC_ACKs of tick k - 1 resolved from write logs (the rest go to the list k_sync_diff streams)
-static void launch_ack_resolve(const Dev& d, uint32_t k, hipStream_t st, bool spec, bool timed) {
+static void launch_ack_resolve(const Dev& d, uint32_t k, hipStream_t st, bool spec, bool timed, bool nodiff = false) {
   if (k == 0 || !d.ackres) return;
   const uint32_t b = (k - 1) & 1;
+  const bool lists = diff_elidable(d);
   const ResArgs ra{d.halt, d.nmsg + b, d.tl_tick, d.tl_n, d.tlog, d.rowk, d.arena[b], d.msgs[b], d.dlist, d.ndl,
                    d.dlist_w, d.ndlw, d.chunk_meta, d.pool_used, d.err, d.pool, d.ctr, d.NL, d.NS, d.MSGCAP, d.NCHUNK, d.POOLCAP, d.NMETA,
                    d.rowk8 ? 1u : 0u, d.lo, d.W, d.MW, d.mlog, d.base_row, d.rx_mask, d.rx_off, d.xa_recv,
-                   (d.ackres & ACKRES_DIRTY) ? d.ms : nullptr, d.W == 1 && d.MW ? 1u : 0u, d.N, d.hflag};
-  hipLaunchKernelGGL(k_ack_resolve, dim3(128), dim3(512), 0, st, ra, k, spec ? 1u : 0u, timed ? 1u : 0u);
+                   (d.ackres & ACKRES_DIRTY) ? d.ms : nullptr, d.W == 1 && d.MW ? 1u : 0u, d.N, d.hflag,
+                   lists ? d.m_head + (size_t)b * d.N : nullptr, lists ? d.m_next + (size_t)b * d.MSGCAP : nullptr,
+                   d.ctr_sh + SH_PINDEC};
+  hipLaunchKernelGGL(k_ack_resolve, dim3(128), dim3(512), 0, st, ra, k, (spec ? 1u : 0u) | (nodiff && lists ? 2u : 0u),
+                     timed ? 1u : 0u);
 }
 
-void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof, bool spec) {
+void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof, bool spec, bool nodiff) {
   hipStream_t st = (hipStream_t)stream;
-  launch_ack_resolve(d, k, st, spec, prof != nullptr);
-  if (k > 0) launch_sync_diff(d, (k - 1) & 1, st, prof ? 1u : 0u, spec ? 1u : 0u, prof);
+  nodiff = nodiff && diff_elidable(d);
+  launch_ack_resolve(d, k, st, spec, prof != nullptr, nodiff);
+  if (k > 0 && !nodiff) launch_sync_diff(d, (k - 1) & 1, st, prof ? 1u : 0u, spec ? 1u : 0u, prof);
+}
+
+void launch_diff_listed(const Dev& d, uint32_t k, void* stream) {
+  if (k > 0) launch_sync_diff(d, (k - 1) & 1, (hipStream_t)stream, 0u);
 }
 
 // link delays: SYNC / SYNC_ACK messages due in the next tick back into this tick's buffer, then the delayed messages
@@ -1163,6 +1224,7 @@ __global__ void __launch_bounds__(256) k_sync_redeliver(Dev d, uint32_t k, uint3
   if (spec) {
     const uint32_t hk = *(volatile uint32_t*)d.halt;
     if (hk != 0 && hk <= k) return;
+    if (*(volatile uint32_t*)(d.halt + 1)) return;  // a diff-halt (at this tick or earlier): member(k) did not run
   }
   __shared__ uint32_t slot[2];
   const uint32_t b = k & 1;
@@ -1210,6 +1272,7 @@ __global__ void __launch_bounds__(256) k_sync_defer(Dev d, uint32_t k, uint32_t 
   if (spec) {
     const uint32_t hk = *(volatile uint32_t*)d.halt;
     if (hk != 0 && hk <= k) return;
+    if (*(volatile uint32_t*)(d.halt + 1)) return;  // a diff-halt (at this tick or earlier): member(k) did not run
   }
   __shared__ int32_t slot;
   const uint32_t b = k & 1, n = min(d.nmsg[b], d.MSGCAP);

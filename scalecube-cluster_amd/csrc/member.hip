@@ -1971,6 +1971,9 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   if (flag & 2u) {  // a speculative batch halted at an earlier tick (this tick's own halt is raised while it runs)
     const uint32_t hv = *(volatile uint32_t*)d.halt;
     if (hv != 0u && hv - 1u < k) return;
+    // a diff-halt, of this tick's lister or an earlier one (one GPU, kernels.hip k_ack_resolve): the host runs that
+    // tick's k_sync_diff first; returning before tick_reset keeps the lists and the pool as the lister left them
+    if (*(volatile uint32_t*)(d.halt + 1) != 0u) return;
   }
   // a speculative launch resets the next tick's counters at its start (nothing in this kernel uses them), so no block
   // waits for the last one at its end: the halt that tick_flag would raise is raised by the member taking a slot

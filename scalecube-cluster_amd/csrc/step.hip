@@ -15,7 +15,9 @@ struct Step {
   uint32_t n;
   uint32_t i = 0;
   uint32_t nb = 0;        // a speculative batch ends at the next scrub tick: the call's ticks before nb
-  bool need_diff = true;  // W == 1: SYNC diff(k) not queued yet (it is queued with the previous tick when it can be)
+  // W == 1: the front of tick k (its lister, and its SYNC diff unless the batch elides it) is not queued yet (it is
+  // queued with the previous tick when it can be)
+  bool need_front = true;
 };
 
 // the event set of the call's idx-th tick, if that tick is timed
@@ -44,26 +46,64 @@ int upload_user_gossips(swim_handle* h, uint32_t k) {
 }
 
 // One GPU, speculative batch: while no gossip slot is in use the host need not look at the flag after every member
-// kernel. The rest of the call is queued as diff / member pairs with no host wait; the member kernel after which
+// kernel. The rest of the call is queued as front / member pairs with no host wait; the member kernel after which
 // a slot is in use raises d.halt, every later launch of the batch returns at once, and the host resumes after
 // that tick with the gossip plane.
+// The front of a tick is its lister and its k_sync_diff. While the handle elides (elide_on), an untimed tick's front is
+// the lister alone: in a cluster whose rows agree it decides every payload and the diff would find two empty lists. A
+// lister that does list something raises the diff-halt of its tick kd (d.halt[1]): every later launch returns at once,
+// member(kd) before its resets, and the host queues diff(kd) over the lists as they stand and goes on from member(kd),
+// without elision until a whole batch has listed nothing (d.halt[2], read with the halt words): a cluster with dirty
+// rows pays one extra host wait per dirty spell, not one per tick. Timed ticks keep their event-carrying diff launch.
 int spec_batch(swim_handle* h, Step& s) {
   const Dev& d = h->d;
   const uint32_t k = (uint32_t)h->tick, i = s.i, nb = s.nb;
+  const bool can = diff_elidable(d) && !h->no_elide, elide = can && h->elide_on;
+  const uint32_t k0 = s.need_front ? k : k + 1u;  // the first tick whose front this batch queues
+  auto front = [&](uint32_t kk, uint32_t jj) {
+    const TickEvents* te = events_of(h, kk, jj);
+    launch_diff(d, kk, h->stream, te, true, elide && !te);
+  };
+  // the ticks of [from, to) that ran without a diff launch
+  auto elided = [&](uint32_t from, uint32_t to) {
+    uint64_t c = 0;
+    for (uint32_t t = std::max(from, 1u); elide && t < to; ++t) c += !prof_timed(h, t);
+    return c;
+  };
   for (uint32_t j = i; j < nb; ++j) {
     const uint32_t kj = k + (j - i);
-    if (s.need_diff) launch_diff(d, kj, h->stream, events_of(h, kj, j), true);
+    if (s.need_front) front(kj, j);
     launch_member(d, kj, h->stream, events_of(h, kj, j), true);
-    s.need_diff = j + 1 == nb;
-    if (!s.need_diff) launch_diff(d, kj + 1, h->stream, events_of(h, kj + 1ull, j + 1), true);
+    s.need_front = j + 1 == nb;
+    if (!s.need_front) front(kj + 1, j + 1);
   }
-  HIPCK(hipMemcpyAsync((void*)(h->hflag + 1), d.halt, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipMemcpyAsync((void*)(h->hflag + 8), d.halt, 12, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
-  const uint32_t hk = h->hflag[1];
-  if (hk == 0) {  // the whole batch ran
+  const uint32_t hk = h->hflag[8], hd = h->hflag[9], listed = h->hflag[10];
+  const bool quiet = listed == h->listed_seen;
+  h->listed_seen = listed;
+  if (hk != 0 && hd != 0) return fail(h, SWIM_EDEVICE, "speculative batch: a gossip halt and a diff-halt");
+  if (hk == 0 && hd == 0) {  // the whole batch ran
+    h->diff_elided += elided(k0, k + (nb - i));
+    h->elide_on = quiet;
     h->tick += nb - i;
     s.i = nb;
     h->gossip_ran = false;
+    return SWIM_OK;
+  }
+  if (hd != 0) {  // lister(kd) listed work and no diff was queued: ticks before kd are complete, member(kd) has not run
+    const uint32_t kd = hd - 1u;
+    if (!elide || kd < k0 || kd >= k + (nb - i) || prof_timed(h, kd))
+      return fail(h, SWIM_EDEVICE, "speculative batch: bad diff-halt tick");
+    HIPCK(hipMemsetAsync(d.halt + 1, 0, 4, h->stream));
+    launch_diff_listed(d, kd, h->stream);
+    h->diff_elided += elided(k0, kd);
+    h->diff_halts++;
+    h->elide_on = false;
+    if (kd > k) h->gossip_ran = false;
+    h->tick = kd;
+    s.i = i + (kd - k);
+    s.need_front = false;  // lister(kd) ran (its counter adds are not idempotent) and diff(kd) is queued
     return SWIM_OK;
   }
   const uint32_t kh = hk - 1u;  // member(kh) ran; the launches after it returned at once
@@ -86,7 +126,9 @@ int spec_batch(swim_handle* h, Step& s) {
   launch_gossip(d, kh, h->stream, events_of(h, kh, ih));
   h->gossip_idle = false;
   h->gossip_ran = true;
-  s.need_diff = true;  // diff(kh + 1) returned at once
+  s.need_front = true;  // the front of kh + 1 returned at once
+  h->diff_elided += elided(k0, kh + 1u);
+  h->elide_on = false;   // gossips change rows: the next batch queues its diffs and looks at what the lister lists
   h->tick = kh + 1ull;
   s.i = ih + 1;
   return SWIM_OK;
@@ -98,13 +140,13 @@ int tick_one_gpu(swim_handle* h, Step& s) {
   const uint32_t k = (uint32_t)h->tick, i = s.i;
   const TickEvents* te = events_of(h, h->tick, i);
   // SYNC diff(k) was queued in the previous iteration, except for the first tick of this call
-  if (s.need_diff) launch_diff(d, k, h->stream, te);
+  if (s.need_front) launch_diff(d, k, h->stream, te);
   launch_member(d, k, h->stream, te, false, h->gossip_ran && !d.fastp4);
   const bool nosync = (d.exp & 256) != 0;  // timing experiment: no per-tick event (gossip plane never launched)
   if (!nosync) HIPCK(hipEventRecord(h->ev_member, h->stream));
   const bool pipe = i + 1 < s.n && !h->no_pipe;
   if (pipe) launch_diff(d, k + 1, h->stream, events_of(h, k + 1ull, i + 1));  // overlaps the wait
-  s.need_diff = !pipe;
+  s.need_front = !pipe;
   if (!nosync) HIPCK(hipEventSynchronize(h->ev_member));  // (a spin wait measured the same here: diff(k+1) hides the wake-up)
   h->gossip_idle = !nosync && h->hflag[0] == 0;
   if (!nosync && !h->gossip_idle) {  // slots, rings and receipt lists sized up before they can overflow

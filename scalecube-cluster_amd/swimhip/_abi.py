@@ -213,7 +213,7 @@ DEBUG_SIGNATURES = {
     "swim_debug_diff_dirty": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
     "swim_debug_dirty_check": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
 }
-DD_NAMES = ["skipped", "streamed", "msg_skipped", "rebases", "dirty_rows"]
+DD_NAMES = ["skipped", "streamed", "msg_skipped", "rebases", "dirty_rows", "pin_decided", "diff_elided", "diff_halts"]
 CAP_NAMES = ["slots", "ring", "receipts", "replay", "history", "growths"]
 
 
@@ -250,7 +250,8 @@ def debug_set_incarnation(lib, handle, m, inc):
 
 def debug_diff_dirty(lib, handle, n=len(DD_NAMES)):
     """{name: count} of the SYNC diff's dirty-chunk skipping since create (include/swimhip_debug.h
-    swim_debug_diff_dirty); n = 4 leaves out dirty_rows, which costs a pass over the key plane."""
+    swim_debug_diff_dirty); n = 4 leaves out dirty_rows, which costs a pass over the key plane (and what follows it:
+    the pinned payloads decided from the masks, the ticks run without a diff launch, the diff-halts)."""
     fn = lib.swim_debug_diff_dirty
     fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_diff_dirty"]
     out = (C.c_uint64 * len(DD_NAMES))()
