@@ -364,7 +364,7 @@ static int alloc_table(swim_handle* h) {
     A(d.dq, (uint64_t)(d.EMAX + 2) * d.DQCAP) Z(d.dq_n, d.EMAX + 2) Z(d.dmark, N)
     A(d.ds_msg, d.DSCAP) A(d.ds_row, (uint64_t)d.DSCAP * d.NS) Z(d.ds_used, d.DSCAP) A(d.ds_free, d.DSCAP) A(d.ds_top, 1)
   }
-  if (d.exp & 512) A(d.wt, (uint64_t)(NL + 255) / 256 * 4 * 16)
+  if (d.exp & EXP_WAVE_CLOCK) A(d.wt, (uint64_t)(NL + 255) / 256 * 4 * 16)
   if (d.fastp4) {
     Z(d.evp_hash, N) Z(d.evp_n, N)
   }
@@ -427,8 +427,8 @@ static int init_state(swim_handle* h) {
       h->hrecv.resize(d.W * std::max(d.XA_PEER, d.XB_PEER));
     }
   }
-  HIPCK(hipHostMalloc((void**)&h->hflag, 64, hipHostMallocMapped | hipHostMallocCoherent));
-  for (int i = 0; i < 16; ++i) h->hflag[i] = 0;
+  HIPCK(hipHostMalloc((void**)&h->hflag, HF_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
+  for (uint32_t i = 0; i < HF_BYTES / 4; ++i) h->hflag[i] = 0;
   HIPCK(hipHostGetDevicePointer((void**)&d.hflag, (void*)h->hflag, 0));
   if ((rc = dalloc_fill(h, &d.hsh, 8, 0)) != 0) return rc;  // (hflag above: all zero)
   HIPCK(hipEventCreateWithFlags(&h->ev_member, hipEventDisableTiming));

@@ -451,11 +451,6 @@ __device__ __forceinline__ void slot_create(const Dev& d, uint32_t g, uint32_t m
 }
 
 // end of a sharded tick (W > 1): the same resets, plus the exchange counters (one block)
-// a launch of a speculative batch that halted at an earlier tick (or at this one, for the kernels after the gate)
-__device__ __forceinline__ bool spec_halted(const Dev& d, uint32_t spec) {
-  return spec && *(volatile uint32_t*)d.halt != 0u;
-}
-
 __device__ __forceinline__ void tick_end(const Dev& d, uint32_t k) {
   uint32_t t = threadIdx.x;
   if (t < 8) d.xn[t] = 0;
@@ -486,7 +481,7 @@ __device__ __forceinline__ void tick_reset(const Dev& d, uint32_t k) {
   *d.pool_used = 0;
   if (d.ackres) *d.ndl = *d.ndlw = 0;
   if (__hip_atomic_load(d.free_top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (int32_t)d.SPR)
-    *(volatile uint32_t*)d.halt = k + 1u;
+    raise_gossip_halt(d.halt, k);
 }
 
 // end of k_member_tick (W == 1, the last block, one thread): reset the per-tick counters the gossip plane of this tick and the SYNC diff and
@@ -500,16 +495,16 @@ __device__ __forceinline__ void tick_flag(const Dev& d, uint32_t k) {
   // (a write to host memory holds the end of the kernel for a round trip over the host link)
   const uint32_t used =
       (uint32_t)((int32_t)d.SPR - __hip_atomic_load(d.free_top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  uint32_t v[6] = {used, 0, 0, 0, 0, 0}, sh[6];
-  if (d.rfill) {  // the previous gossip plane's peaks, for the host's capacity growth (api.hip grow_caps)
-    v[1] = *d.rfill;
-    v[2] = *d.rc_n;
-    v[3] = *d.rp_n;
-    v[4] = *d.slow_n;
-    v[5] = *d.hist_n;
+  uint32_t v[HSH_WORDS] = {used, 0, 0, 0, 0, 0}, sh[HSH_WORDS];  // [HSH_USED], the peaks
+  if (d.rfill) {  // the previous gossip plane's peaks, for the host's capacity growth (grow.hip grow_caps)
+    v[hsh_of(HF_FILL)] = *d.rfill;
+    v[hsh_of(HF_NRC)] = *d.rc_n;
+    v[hsh_of(HF_NRP)] = *d.rp_n;
+    v[hsh_of(HF_NSL)] = *d.slow_n;
+    v[hsh_of(HF_NHIST)] = *d.hist_n;
   }
 #pragma unroll
-  for (int i = 0; i < 6; ++i) sh[i] = d.hsh[i];
+  for (uint32_t i = 0; i < HSH_WORDS; ++i) sh[i] = d.hsh[i];
   d.nmsg[nb] = 0;
   d.arena_used[nb] = 0;
   *d.pool_used = 0;
@@ -517,9 +512,9 @@ __device__ __forceinline__ void tick_flag(const Dev& d, uint32_t k) {
   *d.rc_n = 0;
   if (d.ackres) *d.ndl = *d.ndlw = 0;
 #pragma unroll
-  for (int i = 0; i < 6; ++i)
-    if ((i == 0 || d.rfill) && v[i] != sh[i]) {
-      d.hflag[i == 0 ? 0 : i + 1] = v[i];  // [0] slots in use, [2..6] the peaks
+  for (uint32_t i = 0; i < HSH_WORDS; ++i)
+    if ((i == HSH_USED || d.rfill) && v[i] != sh[i]) {
+      d.hflag[hflag_of(i)] = v[i];
       d.hsh[i] = v[i];
     }
   __threadfence_system();

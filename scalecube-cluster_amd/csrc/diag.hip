@@ -54,7 +54,7 @@ int exp_dump_member_cycles(swim_handle* h) {
   HIPCK(hipMemcpy(c, d.ctr + 8, sizeof(c), hipMemcpyDeviceToHost));
   HIPCK(hipMemset(d.ctr + 8, 0, sizeof(c)));
   fprintf(stderr, "exp: member cycles P0+P1 %llu P2+P3 %llu P4 %llu P5 %llu P6 %llu\n", c[0], c[1], c[2], c[3], c[4]);
-  if (d.exp & 128) {
+  if (d.exp & EXP_CYCLES_MAX) {
     unsigned long long w[2];
     HIPCK(hipMemcpy(w, d.ctr + 14, sizeof(w), hipMemcpyDeviceToHost));
     HIPCK(hipMemset(d.ctr + 14, 0, sizeof(w)));

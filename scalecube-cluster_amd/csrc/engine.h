@@ -12,6 +12,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "spec.h"
 #include "swim_common.h"
 
 namespace swim {
@@ -92,7 +93,7 @@ constexpr uint32_t XINL = 16384;  // RCCL: bytes per peer moved by the fixed-siz
 constexpr uint32_t CSH = 64, CSTRIDE = 64;  // Dev::ctr_sh rows, 512 B apart
 // a row holds 8 counters; row 0's spare words (never summed, zero at create) hold, each on a 128-B line of its own away
 // from the counters' atomics: the three halt words of the speculative batches (Dev::halt), and the pinned live-row
-// payloads the lister decided from the masks (kernels.hip pin_clean; among C_DMSGSKIP). No allocation of their own.
+// payloads the lister decided from the masks (sync_diff.hip pin_clean; among C_DMSGSKIP). No allocation of their own.
 constexpr uint32_t SH_HALT = 16, SH_PINDEC = 32;
 enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29,
            // dirty-chunk skipping of the SYNC diff (one GPU): narrow 2048-subject chunks the lister had
@@ -137,7 +138,7 @@ constexpr uint32_t KF_ABS = 0x200u;
 constexpr uint32_t KF_RES = 0x400u;
 // k_sync_diff's list entries (Dev::dlist, dlist_w: 16 B = message, sender, receiver, payload place): the payload place
 // is the message's payload (arena row or PAY_RX | rx index), NEVER for the live row, DESC_PIN | arena row for a pinned
-// live row, DESC_DEFER for a delayed message (kernels.hip desc_pay)
+// live row, DESC_DEFER for a delayed message (sync_diff.hip desc_pay)
 constexpr uint32_t DESC_PIN = 0x80000000u, DESC_DEFER = 0xFFFFFFFEu;
 // On one GPU the narrow list holds one entry per item (four chunks of one message) with a chunk to stream, and the
 // fourth word is item index << 4 | the item's chunks to stream (k_ack_resolve; the others are known equal, Dev::rdirty)
@@ -331,13 +332,7 @@ struct Dev {
   uint32_t* pending_inc; // [N] host requests for the next tick's P0: bits 2.. updateIncarnation calls, bit 1 leaveCluster
   uint32_t* next_evt; // [N] earliest tick at which a pending path / subscription / fetch needs the member
   uint32_t* mdone;  // finished k_member_tick blocks this tick (the last one runs the end-of-tick resets)
-  // speculative batches (W == 1, gossip plane idle): tick + 1 of the member kernel after which the gossip plane was
-  // needed (0: none); every later k_sync_diff / k_member_tick launch of the batch returns at once.
-  // halt[1], one GPU, batches that queue no k_sync_diff on untimed ticks (step.hip): the diff-halt, tick + 1 of the
-  // lister that listed work for a diff nobody queued (k_ack_resolve); every later launch of the batch returns at once,
-  // member(tick) included, and the host runs that diff. A word of its own: halt[0] = k may also be member(k - 1)'s.
-  // halt[2]: entries the lister has listed since create (the host's re-enable rule)
-  uint32_t* halt;  // [3], adjacent (one copy reads them): ctr_sh + SH_HALT
+  uint32_t* halt;  // [HALT_WORDS] the speculative batches' halt words (spec.h): ctr_sh + SH_HALT
   uint32_t* trk;    // [NL][TRKL] per receiver: subjects its row changed earlier in this tick's P1 (member.hip)
   unsigned long long* tbm;  // [NL][NW] the same subjects as a bitmap (zero between ticks): merged in subject order
   uint32_t NW;       // u64 words per bitmap row ((N + 63) / 64; no SYNC with implicit views: 0)
@@ -381,19 +376,13 @@ struct Dev {
   unsigned long long* wt;   // SWIM_EXP & 512: per-wave timestamps of the latest k_member_tick [waves][16]
   uint32_t* err;            // [8] bits, info...
   const Dev* self;          // device-resident copy of this struct (kernels index it through a pointer)
-  uint32_t* hflag;          // host-mapped: [0] gossip slots in use after this tick's member control (W == 1);
-                            // [1] the halt tick read back after a speculative batch; with rfill: the previous gossip
-                            // plane's largest receipt-ring fill [2], routed receipts [3], replay and slow-path sends
-                            // [4], [5], history entries in use [6]; [7] a narrow chunk was streamed since the
-                            // host's last look at the rebase counters (k_ack_resolve); [8..10] Dev::halt's three
-                            // words read back after a one-GPU speculative batch
-  uint32_t* hsh;            // [8] device copy of what hflag holds (tick_flag writes host memory only on a change):
-                            // hsh[0] mirrors hflag[0], hsh[1..5] mirror hflag[2..6]
+  uint32_t* hflag;          // host-mapped flag block, HF_BYTES (spec.h HFlag)
+  uint32_t* hsh;            // [8] device copy of what tick_flag publishes in hflag (spec.h HSH_USED ...)
   uint32_t* rfill;          // [1] W == 1: largest ring fill (rtail - rhead) after this tick's receipts (grow_caps)
   uint32_t* dbg_send;       // debugging aid (SWIM_SEND_LOG=cap): [cap][5] tick, sender, gid lo, gid hi, target
   uint32_t* dbg_send_n;
   uint32_t dbg_send_cap;
-  uint32_t exp;  // timing experiments only (SWIM_EXP): 1 = no infectedFrom replay, 2 = no per-target work
+  uint32_t exp;  // timing experiments only (SWIM_EXP): the EXP_ bits of spec.h
   // runtime capacities of the fast structures (<= the compile-time sizes TRK, ULOG, CREQ, CWMAX, CEV, MQ, SORT_MAX);
   // SWIM_CAPS lowers them so that tests drive every exact fallback path (include/swimhip_debug.h)
   uint32_t trk_cap, ulog_cap, creq_cap, cwmax_cap, cev_cap, mq_cap, sort_cap;
@@ -506,10 +495,10 @@ void launch_init(const Dev& d, void* stream);
 // single GPU, per tick k: launch_diff(k) (k > 0), launch_member(k) (+ host flag), then launch_gossip(k) if the flag
 // says a gossip slot is in use; launch_diff(k+1) may be queued before launch_gossip(k)
 // spec: a launch of a speculative batch (it returns at once once d.halt is set)
-// nodiff (one GPU with dirty masks and the 8-bit plane; else ignored): only the lister is queued, told that no
-// k_sync_diff follows it; launch_diff_listed is that diff alone, for the host after a diff-halt (not speculative)
-void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, bool spec = false,
-                 bool nodiff = false);
+// launch_diff's ls: LS_SPEC, | LS_NODIFF (one GPU with dirty masks and the 8-bit plane; else ignored): only the lister
+// is queued, told that no k_sync_diff follows it; launch_diff_listed is that diff alone, for the host after a diff-halt
+// (not speculative)
+void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, uint32_t ls = 0u);
 void launch_diff_listed(const Dev& d, uint32_t k, void* stream);
 // split: the previous tick ran the gossip plane (routed receipts for P4: k_member_tick parks the members with many,
 // k_inbox_apply runs their P4, a second k_member_tick launch their P5 and P6)
@@ -546,5 +535,16 @@ void launch_key_set(const Dev& d, uint32_t m, uint32_t s, uint32_t key, void* st
 // row's chunk counted into *viol, the set bits of the masks summed into *ndirty; ref: [NCHUNK] scratch
 void launch_dirty_check(const Dev& d, uint32_t* viol, uint32_t* ndirty, uint32_t* ref, void* stream);
 void launch_dbg_holders(const Dev& d, uint32_t first, uint32_t n, uint32_t* out, void* stream);  // swim_debug_holders
+// launchers one kernel file calls in another
+static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+void launch_gossip_send(const Dev& d, uint32_t k, hipStream_t st, const TickEvents* prof);  // gossip.hip
+void launch_gossip_apply(const Dev& d, uint32_t k, hipStream_t st);
+void launch_unpack_b(const Dev& d, uint32_t k, hipStream_t st);
+void launch_scan(const uint32_t* in, uint32_t* out, uint32_t* part, uint32_t n, hipStream_t st);  // route.hip
+void launch_receipt_routing(const Dev& d, hipStream_t st);
+// sync_delay.hip (link delays): after the member kernel of tick k, the stored messages due in tick k + 1 back into the
+// inbound list; the delayed messages of tick k into the store (W > 1: after k_unpack_a)
+void launch_sync_redeliver(const Dev& d, uint32_t k, hipStream_t st, bool spec);
+void launch_sync_defer(const Dev& d, uint32_t k, hipStream_t st, bool spec);
 
 }  // namespace swim

@@ -758,7 +758,7 @@ __global__ void __launch_bounds__(256, 8) k_gossip_send(const Dev* __restrict__ 
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint64_t items = (uint64_t)ntl * nag;
   const int ep = epoch_at(d, k);
-  if ((d.exp & 4) && blockIdx.x == 0 && threadIdx.x == 0) {  // work units: (target, group) items, their sender words
+  if ((d.exp & EXP_GOSSIP_WORK) && blockIdx.x == 0 && threadIdx.x == 0) {  // work units: (target, group) items, their sender words
     uint64_t pairs = 0;
     for (uint32_t i = 0; i < ntl; ++i) pairs += d.tin_cnt[d.tlist[i]];
     atomicAdd(&d.ctr[C_XU], (unsigned long long)items);
@@ -798,12 +798,12 @@ __global__ void __launch_bounds__(256, 8) k_gossip_send(const Dev* __restrict__ 
           w &= ~wr;
         }
       }
-      if ((w | wr) && (d.exp & 4)) st[0]++;
+      if ((w | wr) && (d.exp & EXP_GOSSIP_WORK)) st[0]++;
       // (the slow path past the contact cache replays from a full scan of both round logs)
       const bool slow = ci == CIN_SLOW;
       if (__ballot(wr != 0ull)) {
         const uint32_t c = (uint32_t)__popcll(wr);
-        if (d.exp & 4) st[1] += c;
+        if (d.exp & EXP_GOSSIP_WORK) st[1] += c;
         fb_add(d, slow ? FB_CEV_SLOW : FB_REPLAY, c);
         uint32_t jr = wave_reserve(d.rp_n, slow ? 0u : c), js = wave_reserve(d.slow_n, slow ? c : 0u);
         uint32_t j = slow ? js : jr;
@@ -861,7 +861,7 @@ __global__ void __launch_bounds__(256, 8) k_gossip_send(const Dev* __restrict__ 
         continue;
       }
       if (!cand) continue;
-      if (d.exp & 4) st[3] += (uint32_t)__popcll(cand);
+      if (d.exp & EXP_GOSSIP_WORK) st[3] += (uint32_t)__popcll(cand);
       if (ep < 0) {
         set_err(d, E_EPOCH);
         continue;
@@ -917,7 +917,7 @@ __global__ void __launch_bounds__(256, 8) k_gossip_send(const Dev* __restrict__ 
       }
     }
   }
-  if (d.exp & 4)
+  if (d.exp & EXP_GOSSIP_WORK)
     for (int q2 = 0; q2 < 4; ++q2)
       if (st[q2]) atomicAdd(&d.ctr[8 + q2], (unsigned long long)st[q2]);
   for (uint32_t o = 32; o > 0; o >>= 1) sends += __shfl_xor(sends, o);
@@ -990,11 +990,11 @@ __global__ void __launch_bounds__(256, 8) k_gossip_replay(const Dev* __restrict_
     const uint32_t t = d.T[ms], c = s_ctick(s_get(d, g, m, k + d.lat)), ci = d.cin[ms];  // m holds g: a current entry
     const uint64_t gid = d.slot_gid[g];
     const bool maybe = ci >= d.slot_ctick[g] && ci + d.lat + dmax(d) >= c;
-    if (d.exp & 4) {  // timing experiment: replay items that reach the contact replay, and those it blocks
+    if (d.exp & EXP_GOSSIP_WORK) {  // timing experiment: replay items that reach the contact replay, and those it blocks
       if (maybe) atomicAdd(&d.ctr[10], 1ull);
     }
     if (maybe && blocked_pair_cached(d, m, t, g, gid, k, c, d.cev + (size_t)ms * CEVW)) {
-      if (d.exp & 4) atomicAdd(&d.ctr[12], 1ull);
+      if (d.exp & EXP_GOSSIP_WORK) atomicAdd(&d.ctr[12], 1ull);
       continue;
     }
     sends++;
@@ -1074,7 +1074,7 @@ __global__ void k_dq_reset(Dev d, uint32_t k) { d.dq_n[(k + d.lat) % (d.EMAX + 2
 // become present earlier in the tick). User gossips are always routed (each one emits a GOSSIP event).
 __device__ __forceinline__ bool receipt_matters(const Dev& d, uint32_t t, uint32_t g, uint32_t k4) {
   const uint32_t subj = d.slot_subj[g];
-  if (subj == USER_SUBJ || (d.exp & 8)) return true;  // SWIM_EXP & 8: route every receipt (debugging aid)
+  if (subj == USER_SUBJ || (d.exp & EXP_ROUTE_ALL)) return true;  // SWIM_EXP & 8: route every receipt (debugging aid)
   const uint64_t key = d.slot_key[g];
   const uint32_t r0 = d.rowk[lidx(d, t) * d.NS + subj], s1 = rec_status(key);
   if ((r0 & 3u) == ST_ABSENT || overrides(s1, rec_inc(key), r0 & 3u, r0 >> 2)) return true;
@@ -1274,9 +1274,6 @@ __global__ void k_unpack_b(Dev d, uint32_t k) {
 
 // ------------------------------------------------------------------------------------------------------------
 // host launchers
-static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
-void launch_scan(const uint32_t* in, uint32_t* out, uint32_t* part, uint32_t n, hipStream_t st);  // kernels.hip
-void launch_receipt_routing(const Dev& d, hipStream_t st);                                         // kernels.hip
 
 constexpr uint32_t SEND_GRID = 4096;  // 16 blocks per CU, grid-stride
 

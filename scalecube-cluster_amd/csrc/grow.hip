@@ -142,7 +142,7 @@ static int grow_caps_(swim_handle* h) {
   if (!d.rfill) return SWIM_OK;
   // (a row shard publishes only the ring fill and the history entries, grow_caps_shard: [0], [3..5] stay 0)
   const volatile uint32_t* f = h->hflag;
-  const uint64_t used = f[0], fill = f[2], nrc = f[3], nrp = f[4], nsl = f[5], nhist = f[6];
+  const uint64_t used = f[HF_USED], fill = f[HF_FILL], nrc = f[HF_NRC], nrp = f[HF_NRP], nsl = f[HF_NSL], nhist = f[HF_NHIST];
   const uint64_t N = d.N;
   const bool gs = used > d.SPR / 2 && d.SPR < (1u << 22), gr = fill > d.BCAP / 2 && d.BCAP < (1u << 30);
   const bool grc = nrc > d.RCAP / 4 && d.RCAP < (1u << 30), grp = (nrp > d.RPCAP / 4 || nsl > d.SLOWCAP / 4) && d.RPCAP < (1u << 30);
@@ -205,10 +205,10 @@ int grow_caps_shard(swim_handle* h) {
   HIPCK(hipMemsetAsync(d.rfill, 0, 4, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   volatile uint32_t* f = h->hflag;
-  f[0] = 0;  // slots: not grown on a shard
-  f[2] = v[0];
-  f[3] = f[4] = f[5] = 0;
-  f[6] = v[1];
+  f[HF_USED] = 0;  // slots: not grown on a shard
+  f[HF_FILL] = v[0];
+  f[HF_NRC] = f[HF_NRP] = f[HF_NSL] = 0;
+  f[HF_NHIST] = v[1];
   return grow_caps(h);
 }
 

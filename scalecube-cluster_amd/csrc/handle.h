@@ -6,6 +6,9 @@
 //   diag.hip      SWIM_STATS / SWIM_EXP dumps, profile events
 //   group.hip     swim_config.n_gpus > 1: one handle over several shard handles
 //   api.hip       the other extern "C" entry points: fault injection, readback
+// The device side (engine.h, spec.h, dev_util.h): member.hip (member control), sync_diff.hip (SYNC diff and its lister),
+// sync_delay.hip (delayed-SYNC store), route.hip (receipt routing), gossip.hip (gossip data plane), shard.hip (row-shard
+// pack / unpack), kernels.hip (initialisation, state hashes, the tick launchers).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -72,7 +75,7 @@ struct swim_handle {
   // (step.hip spec_batch); SWIM_NO_ELIDE keeps a diff launch on every tick (measurements, the tests' reference path)
   bool no_elide = getenv("SWIM_NO_ELIDE") != nullptr;
   bool elide_on = true;       // off after a diff-halt or a gossip plane, on again after a batch that listed nothing
-  uint32_t listed_seen = 0;   // Dev::halt[2] as last read
+  uint32_t listed_seen = 0;   // Dev::halt[HALT_LISTED] as last read
   uint64_t diff_elided = 0;   // ticks run without a k_sync_diff launch (swim_debug_diff_dirty)
   uint64_t diff_halts = 0;    // batches stopped by a diff-halt
   bool gossip_idle = false;  // W == 1: no gossip slot was in use after the latest member kernel

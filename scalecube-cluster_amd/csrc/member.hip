@@ -404,7 +404,7 @@ __device__ __forceinline__ void flush_spreads(ML& L) {
   if (n == 0) return;
   L.nsp = 0;
   const Dev& d = *L.d;
-  if (L.spec) *(volatile uint32_t*)d.halt = L.k + 1u;  // a slot in use: the batch stops after this tick
+  if (L.spec) raise_gossip_halt(d.halt, L.k);  // a slot in use: the batch stops after this tick
   const int base = atomicSub(d.free_top, (int)n) - (int)n;
   uint32_t rt = d.rtail[L.m];  // only this lane appends to the member's ring in this kernel
   for (uint32_t i = 0; i < n; ++i) {
@@ -942,7 +942,7 @@ __device__ __forceinline__ void merge_payload(ML& L, uint32_t mi, uint32_t reaso
   const uint32_t nt = L.ntrk;
   const bool bmap = nt > d.trk_cap;  // many subjects changed earlier in this tick: walk the bitmap
   if (bmap) fb_add(d, FB_TRK_WALK);
-  if (d.exp & 128) {  // timing experiments: full walks, largest candidate count
+  if (d.exp & EXP_CYCLES_MAX) {  // timing experiments: full walks, largest candidate count
     if (bmap) atomicAdd(&d.ctr[14], 1ull);
     atomicMax(&d.ctr[15], (unsigned long long)mm.ncand);
   }
@@ -1197,16 +1197,16 @@ __device__ __forceinline__ void member_tick_body(const Dev& d, uint32_t m, uint3
   }
   // SWIM_EXP & 16 (timing experiment): shader cycles per phase summed over members, ctr[8..12]
   // SWIM_EXP & 128: the largest per-member cycles of each phase instead (which phase makes the longest lane)
-  const bool prof = (d.exp & (16 | 128)) != 0;
+  const bool prof = (d.exp & EXP_CYCLES) != 0;
   unsigned long long tp = prof ? clock64() : 0;
   // SWIM_EXP & 512: the wave's first busy lane stamps the wall clock after each phase group (wt[4 + slot])
   // (the first lane active at the lap stamps it: a lap inside a branch times the lanes that took it)
   auto lap = [&](int slot) {
-    if ((d.exp & 512) && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)__ballot(1)) - 1))
+    if ((d.exp & EXP_WAVE_CLOCK) && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)__ballot(1)) - 1))
       d.wt[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + 4 + slot] = wall_clock64();
     if (!prof || slot > 4) return;  // (slots 5-10: finer wall-clock laps only)
     const unsigned long long t = clock64();
-    if (d.exp & 16)
+    if (d.exp & EXP_CYCLES_SUM)
       atomicAdd(&d.ctr[8 + slot], t - tp);
     else
       atomicMax(&d.ctr[8 + slot], t - tp);
@@ -1562,7 +1562,7 @@ __device__ __forceinline__ void member_tick_body(const Dev& d, uint32_t m, uint3
   }
 
   // ---- P4 gossip first receipts in gossip-id order -> onMembershipGossip (:401-408) ----
-  // only the receipts that can change the row were routed (receipt_matters, kernels.hip); the others were counted
+  // only the receipts that can change the row were routed (receipt_matters, gossip.hip); the others were counted
   // as record compares by the triage
   {
     uint32_t off = d.rc_off[m], n = d.rc_cnt[m];
@@ -1961,25 +1961,21 @@ __global__ void __launch_bounds__(256) k_inbox_apply(const Dev* __restrict__ dp,
 // control path for them: a wave holds one kind of work, so it does not serialise the latency chains of a ping, a
 // ping hop and an ack arrival, and no wave runs mostly idle lanes. Counters are summed across the wave first: 10^4
 // pingers per tick adding to one word would serialise on that address. With `flag` (W == 1) the block that finishes
-// last runs the end-of-tick resets and raises the host flag. flag: 1 = W == 1 (end-of-tick work), 2 = a launch of a
-// speculative batch.
+// last runs the end-of-tick resets and raises the host flag. flag: MT_END = W == 1 (end-of-tick work), MT_SPEC = a
+// launch of a speculative batch (spec.h).
 // (MODE: BODY_FULL, or the two launches around k_inbox_apply, BODY_SPLIT and BODY_RESUME: three kernels, each with its
 // own register allocation, so the steady-state one keeps the code it had before the split)
 template <uint32_t MODE>
 __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict__ dp, uint32_t k, uint32_t flag) {
   const Dev& d = *dp;  // global, not kernarg: taking its address must not copy ~1 KB into per-lane scratch
-  if (flag & 2u) {  // a speculative batch halted at an earlier tick (this tick's own halt is raised while it runs)
-    const uint32_t hv = *(volatile uint32_t*)d.halt;
-    if (hv != 0u && hv - 1u < k) return;
-    // a diff-halt, of this tick's lister or an earlier one (one GPU, kernels.hip k_ack_resolve): the host runs that
-    // tick's k_sync_diff first; returning before tick_reset keeps the lists and the pool as the lister left them
-    if (*(volatile uint32_t*)(d.halt + 1) != 0u) return;
-  }
+  // a speculative batch halted at an earlier tick (this tick's own halt is raised while it runs), or by a diff-halt:
+  // returning before tick_reset keeps the lists and the pool as the lister left them (spec.h)
+  if (mt_spec(flag) && halted_member(d.halt, k)) return;
   // a speculative launch resets the next tick's counters at its start (nothing in this kernel uses them), so no block
   // waits for the last one at its end: the halt that tick_flag would raise is raised by the member taking a slot
-  if ((flag & 3u) == 3u && blockIdx.x == 0 && threadIdx.x == 0) tick_reset(d, k);
+  if (mt_spec_one_gpu(flag) && blockIdx.x == 0 && threadIdx.x == 0) tick_reset(d, k);
   // SWIM_EXP & 512 (timing experiment): wall clock of each wave at entry, after triage, after its bodies, at exit
-  const bool wtime = (d.exp & 512) != 0;
+  const bool wtime = (d.exp & EXP_WAVE_CLOCK) != 0;
   unsigned long long* wt = wtime ? d.wt + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 : nullptr;
   if (wtime && (threadIdx.x & 63) == 0) wt[0] = wall_clock64();
   __shared__ uint32_t wc[4][4];  // [wave][class] busy members
@@ -2038,9 +2034,9 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   // SWIM_EXP & 32 / 64 (timing experiments, wrong results): skip the bodies of class 0 / of classes 1-3
   if (__ballot(me != NEVER)) {  // waves with no busy member skip to the end
     unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const bool skip = ((d.exp & 32) && mcls == 0) || ((d.exp & 64) && mcls != 0);
+    const bool skip = ((d.exp & EXP_SKIP_CLASS0) && mcls == 0) || ((d.exp & EXP_SKIP_CLASS123) && mcls != 0);
     if (me != NEVER && !skip)
-      member_tick_body<MODE>(d, me, k, cnt, cw, &cw_n, (flag & 3u) == 3u);
+      member_tick_body<MODE>(d, me, k, cnt, cw, &cw_n, mt_spec_one_gpu(flag));
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       unsigned long long v = cnt[i];
@@ -2077,7 +2073,7 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
     __syncthreads();
   }
   if (wtime && (threadIdx.x & 63) == 0) wt[3] = wall_clock64();
-  if ((flag & 3u) != 1u) return;
+  if (!mt_closes_tick(flag)) return;
   if (!last_block_ticket(d.mdone, gridDim.x) || threadIdx.x != 0) return;
   *d.mdone = 0;
   if (resume) *d.nhv = 0;  // every block has read the list

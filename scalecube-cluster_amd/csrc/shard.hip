@@ -62,7 +62,7 @@ __device__ __forceinline__ uint32_t block_excl_256(uint32_t v, uint32_t* sh, uin
 // `rank` queues the local messages for the next tick's inbound list. (A steady-state sharded tick was member kernel,
 // route, pack, chunk launches back to back: two launches and their drains fewer.)
 __global__ void __launch_bounds__(256) k_pack_all(Dev d, uint32_t b, uint32_t spec) {
-  if (spec_halted(d, spec)) return;
+  if (spec && halted(d.halt)) return;
   const uint32_t q = blockIdx.y, x = blockIdx.x, t = threadIdx.x;
   __shared__ uint32_t sh[8], tot_sh[2];
   const uint32_t n = min(d.nmsg[b], d.MSGCAP);
@@ -242,7 +242,7 @@ __device__ void msgs_commit(const Dev& d, uint32_t b) {
   }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-    if (d.mtmp[i].kind & KF_DEFER) continue;  // delivered later: stored by k_sync_defer_x at the end of this tick
+    if (d.mtmp[i].kind & KF_DEFER) continue;  // delivered later: stored by k_sync_defer<true> at the end of this tick
     const uint32_t old = atomicExch(&d.m_head[(size_t)b * d.N + d.mtmp[i].dst], i);
     d.m_next[(size_t)b * d.MSGCAP + i] = old;
     if (old != NEVER) {
@@ -258,11 +258,11 @@ __device__ void msgs_commit(const Dev& d, uint32_t b) {
 // (k_tick_end): the steady-state tick after exchange A is this one launch.
 __device__ __forceinline__ bool spec_gate(const Dev& d);
 __global__ void __launch_bounds__(256) k_unpack_a(Dev d, uint32_t k, uint32_t end, uint32_t spec) {
-  if (spec_halted(d, spec)) return;
+  if (spec && halted(d.halt)) return;
   // the gate of a speculative batch, evaluated by every block from the same count words: all of them see the same
   // answer, and one raises d.halt for the host
   if (spec && spec_gate(d)) {
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *d.halt = k + 1u;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) raise_gate_halt(d.halt, k);
     return;
   }
   const uint32_t p = blockIdx.y;
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(256) k_inline_in(const uint8_t* irecv, uint8_t
                                                    const unsigned long long* scnt, unsigned long long* rcnt,
                                                    unsigned long long* host, uint32_t W, const uint32_t* halt,
                                                    uint32_t XI) {
-  if (halt && *(volatile const uint32_t*)halt) return;  // speculative batch: halted at an earlier tick
+  if (halt && halted(halt)) return;  // speculative batch: halted at an earlier tick
   const uint32_t p = blockIdx.x;
   const uint64_t* src = (const uint64_t*)(irecv + (size_t)p * XI);
   const unsigned long long w = src[0];

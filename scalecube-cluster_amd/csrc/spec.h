@@ -1,0 +1,144 @@
+// spec.h — the halt protocol of the speculative batches, the launch flags that carry it, the host-mapped flag block
+// and the SWIM_EXP bits: everything a kernel or a host path must agree on to take part in a batch (step.hip).
+//
+// A speculative batch is a run of ticks queued with no host wait (one GPU: spec_batch; row shards over RCCL:
+// shard_spec_batch). Three device words, Dev::halt, decide which of the queued launches still do anything. A launch of
+// tick k reads them at its start (volatile loads; hg = halt[HALT_GOSSIP], hd = halt[HALT_DIFF]) and returns at once by
+// the rule of its kernel; nothing waits on the device, and the host reads the words back after the batch.
+//
+//   kernel (launch of tick k)         predicate             returns at once when
+//   k_ack_resolve (the lister)        halted_lister         hg != 0, or hd != 0 && hd != k + 1
+//   k_sync_diff                       halted_diff           hg != 0 or hd != 0
+//   k_member_tick_t                   halted_member         hg != 0 && hg <= k, or hd != 0
+//   k_sync_redeliver<false>           halted_member         (the same)
+//   k_sync_defer<false>               halted_member         (the same)
+//   k_sync_redeliver<true>            halted_before         hg != 0 && hg <= k
+//   k_sync_defer<true>                halted_uncommitted    hg != 0 && hg <= k + 1
+//   k_pack_all, k_unpack_a,           halted                hg != 0
+//   k_inline_in
+//
+// Why the rules differ:
+// * the lister and the diff of tick k are queued before member(k - 1)'s successors know whether that member kernel
+//   took a gossip slot, so any gossip halt (hg = k at the latest) stops them: the host queues them again after the
+//   gossip plane. The lister ignores the diff-halt of its own tick, hd == k + 1, which another block of the same
+//   launch raised: its list must be complete for the diff the host then runs. The diff is only queued when its lister
+//   raises no diff-halt, so either word stops it.
+// * member(k) raises hg = k + 1 itself while it runs (a member that takes a slot, or tick_reset): its own blocks and
+//   the one-GPU delayed-SYNC kernels of tick k, which move that tick's messages, go on; only a halt of an earlier tick
+//   (hg <= k) stops them. A diff-halt of tick k or earlier means member(k) must not run before the host has run that
+//   diff: returning before tick_reset keeps the lists and the pool as the lister left them.
+// * a row shard never raises a diff-halt (its batches always queue the diff), and its gossip halt is raised by the
+//   gate in k_unpack_a(k), after exchange A: k_sync_redeliver<true>(k) runs before the gate and stops on an earlier
+//   tick's halt only; k_sync_defer<true>(k) runs after it and skips tick k itself too, because its inbound list was
+//   not committed (the host's path stores that tick's delayed messages); k_pack_all, k_unpack_a and k_inline_in carry
+//   no tick of their own and stop on any halt (the kernels after the gate: on this tick's, too).
+//
+// The raises: raise_gossip_halt (a member taking a slot, tick_reset), raise_gate_halt (k_unpack_a's gate),
+// raise_diff_halt and count_listed (the lister). The host clears a word after it has acted on it.
+#pragma once
+#include <stdint.h>
+
+namespace swim {
+
+// ---- Dev::halt ----
+enum HaltWord : uint32_t {
+  // tick + 1 of the member kernel after which the gossip plane is needed (0: none); row shards: of the tick whose
+  // exchange A needs the host (k_unpack_a's gate)
+  HALT_GOSSIP = 0,
+  // one GPU, batches that queue no k_sync_diff on untimed ticks (step.hip): the diff-halt, tick + 1 of the lister that
+  // listed work for a diff nobody queued (k_ack_resolve); every later launch of the batch returns at once, member(tick)
+  // included, and the host runs that diff. A word of its own: HALT_GOSSIP = k may also be member(k - 1)'s.
+  HALT_DIFF = 1,
+  // entries the lister has listed since create (the host's re-enable rule)
+  HALT_LISTED = 2,
+  HALT_WORDS = 3  // adjacent: one copy reads them back
+};
+
+__device__ __forceinline__ bool halted(const uint32_t* halt) { return *(volatile const uint32_t*)halt != 0u; }
+__device__ __forceinline__ bool halted_diff(const uint32_t* halt) {
+  return (*(volatile const uint32_t*)(halt + HALT_GOSSIP) | *(volatile const uint32_t*)(halt + HALT_DIFF)) != 0u;
+}
+__device__ __forceinline__ bool halted_lister(const uint32_t* halt, uint32_t k) {
+  const uint32_t hg = *(volatile const uint32_t*)(halt + HALT_GOSSIP), hd = *(volatile const uint32_t*)(halt + HALT_DIFF);
+  return hg || (hd && hd != k + 1u);
+}
+__device__ __forceinline__ bool halted_before(const uint32_t* halt, uint32_t k) {
+  const uint32_t hg = *(volatile const uint32_t*)(halt + HALT_GOSSIP);
+  return hg != 0u && hg - 1u < k;
+}
+__device__ __forceinline__ bool halted_uncommitted(const uint32_t* halt, uint32_t k) { return halted_before(halt, k + 1u); }
+__device__ __forceinline__ bool halted_member(const uint32_t* halt, uint32_t k) {
+  return halted_before(halt, k) || *(volatile const uint32_t*)(halt + HALT_DIFF) != 0u;
+}
+
+__device__ __forceinline__ void raise_gossip_halt(uint32_t* halt, uint32_t k) {
+  *(volatile uint32_t*)(halt + HALT_GOSSIP) = k + 1u;
+}
+// (a plain store: one thread of the grid, read by later launches only)
+__device__ __forceinline__ void raise_gate_halt(uint32_t* halt, uint32_t k) { halt[HALT_GOSSIP] = k + 1u; }
+__device__ __forceinline__ void raise_diff_halt(uint32_t* halt, uint32_t k) {
+  *(volatile uint32_t*)(halt + HALT_DIFF) = k + 1u;
+}
+__device__ __forceinline__ void count_listed(uint32_t* halt, uint32_t n) { atomicAdd(halt + HALT_LISTED, n); }
+
+// ---- launch flags ----
+// k_member_tick_t's flag
+enum : uint32_t {
+  MT_END = 1u,   // one GPU: the launch does the end-of-tick work (the last block: tick_flag)
+  MT_SPEC = 2u,  // a launch of a speculative batch
+};
+constexpr bool mt_spec(uint32_t flag) { return (flag & MT_SPEC) != 0u; }
+// a one-GPU speculative launch: the resets at its start (tick_reset), the member taking a slot raises the halt
+constexpr bool mt_spec_one_gpu(uint32_t flag) { return (flag & (MT_END | MT_SPEC)) == (MT_END | MT_SPEC); }
+// the last block to finish closes the tick (tick_flag): one GPU, not speculative
+constexpr bool mt_closes_tick(uint32_t flag) { return (flag & (MT_END | MT_SPEC)) == MT_END; }
+
+// the lister's spec (k_ack_resolve), and what launch_diff takes
+enum : uint32_t {
+  LS_SPEC = 1u,    // a launch of a speculative batch
+  LS_NODIFF = 2u,  // no k_sync_diff follows this launch: a block that lists an entry raises the diff-halt of its tick
+};
+
+// ---- the host-mapped flag block (Dev::hflag, swim_handle::hflag) ----
+enum HFlag : uint32_t {
+  HF_USED = 0,        // gossip slots in use after this tick's member control (W == 1)
+  HF_SHARD_HALT = 1,  // HALT_GOSSIP read back after a speculative sharded batch
+  // with Dev::rfill, the previous gossip plane's peaks (grow.hip): the largest receipt-ring fill, routed receipts,
+  // replay sends, slow-path sends, history entries in use
+  HF_PEAK0 = 2,
+  HF_FILL = HF_PEAK0,
+  HF_NRC,
+  HF_NRP,
+  HF_NSL,
+  HF_NHIST,
+  HF_STREAMED = 7,  // a narrow chunk was streamed since the host's last look at the rebase counters (k_ack_resolve)
+  HF_HALT = 8,      // Dev::halt's words read back after a one-GPU speculative batch
+  HF_WORDS = HF_HALT + HALT_WORDS
+};
+constexpr uint32_t HF_NPEAK = 5, HF_BYTES = 64;
+static_assert(HF_NHIST + 1 == HF_PEAK0 + HF_NPEAK && HF_NHIST < HF_STREAMED, "the peak words are adjacent");
+static_assert(HALT_GOSSIP == 0 && HALT_DIFF == 1 && HALT_LISTED == 2 && HALT_WORDS == 3,
+              "the halt words are adjacent: one copy reads them back, word w into hflag[HF_HALT + w]");
+static_assert(HF_WORDS * 4 <= HF_BYTES, "the flag block fits its allocation");
+// Dev::hsh, the device copy of what tick_flag publishes (it writes host memory only on a change): the slots in use, then
+// the peaks in HFlag's order
+enum : uint32_t { HSH_USED = 0, HSH_PEAK0 = 1, HSH_WORDS = HSH_PEAK0 + HF_NPEAK };
+constexpr uint32_t hsh_of(HFlag w) { return w == HF_USED ? HSH_USED : HSH_PEAK0 + (w - HF_PEAK0); }  // hflag word w's copy
+constexpr uint32_t hflag_of(uint32_t i) { return i == HSH_USED ? HF_USED : HF_PEAK0 + (i - HSH_PEAK0); }  // and back
+
+// ---- SWIM_EXP bits (Dev::exp): timing experiments and debugging aids; most give wrong results ----
+enum : uint32_t {
+  EXP_NO_REPLAY = 1,      // no infectedFrom replay (no longer read)
+  EXP_NO_TARGETS = 2,     // no per-target work (no longer read)
+  EXP_GOSSIP_WORK = 4,    // gossip-send work units counted (ctr[8..12], ctr[16..19]) and dumped after each step
+  EXP_ROUTE_ALL = 8,      // route every receipt to P4 (debugging aid)
+  EXP_CYCLES_SUM = 16,    // member-kernel shader cycles per phase, summed over members (ctr[8..12])
+  EXP_SKIP_CLASS0 = 32,   // skip the member bodies of class 0
+  EXP_SKIP_CLASS123 = 64, // skip the member bodies of classes 1-3
+  EXP_CYCLES_MAX = 128,   // the largest per-member cycles of each phase instead; full walks, largest candidate count
+  EXP_NO_EVENT = 256,     // no per-tick event or host wait (the gossip plane is never launched)
+  EXP_WAVE_CLOCK = 512,   // per-wave wall-clock stamps of the latest member kernel (Dev::wt)
+  EXP_CYCLES = EXP_CYCLES_SUM | EXP_CYCLES_MAX,
+};
+
+}  // namespace swim

@@ -51,9 +51,9 @@ int upload_user_gossips(swim_handle* h, uint32_t k) {
 // that tick with the gossip plane.
 // The front of a tick is its lister and its k_sync_diff. While the handle elides (elide_on), an untimed tick's front is
 // the lister alone: in a cluster whose rows agree it decides every payload and the diff would find two empty lists. A
-// lister that does list something raises the diff-halt of its tick kd (d.halt[1]): every later launch returns at once,
+// lister that does list something raises the diff-halt of its tick kd (HALT_DIFF): every later launch returns at once,
 // member(kd) before its resets, and the host queues diff(kd) over the lists as they stand and goes on from member(kd),
-// without elision until a whole batch has listed nothing (d.halt[2], read with the halt words): a cluster with dirty
+// without elision until a whole batch has listed nothing (HALT_LISTED, read with the halt words): a cluster with dirty
 // rows pays one extra host wait per dirty spell, not one per tick. Timed ticks keep their event-carrying diff launch.
 int spec_batch(swim_handle* h, Step& s) {
   const Dev& d = h->d;
@@ -62,7 +62,7 @@ int spec_batch(swim_handle* h, Step& s) {
   const uint32_t k0 = s.need_front ? k : k + 1u;  // the first tick whose front this batch queues
   auto front = [&](uint32_t kk, uint32_t jj) {
     const TickEvents* te = events_of(h, kk, jj);
-    launch_diff(d, kk, h->stream, te, true, elide && !te);
+    launch_diff(d, kk, h->stream, te, LS_SPEC | (elide && !te ? LS_NODIFF : 0u));
   };
   // the ticks of [from, to) that ran without a diff launch
   auto elided = [&](uint32_t from, uint32_t to) {
@@ -77,9 +77,10 @@ int spec_batch(swim_handle* h, Step& s) {
     s.need_front = j + 1 == nb;
     if (!s.need_front) front(kj + 1, j + 1);
   }
-  HIPCK(hipMemcpyAsync((void*)(h->hflag + 8), d.halt, 12, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipMemcpyAsync((void*)(h->hflag + HF_HALT), d.halt, HALT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
-  const uint32_t hk = h->hflag[8], hd = h->hflag[9], listed = h->hflag[10];
+  const volatile uint32_t* hw = h->hflag + HF_HALT;
+  const uint32_t hk = hw[HALT_GOSSIP], hd = hw[HALT_DIFF], listed = hw[HALT_LISTED];
   const bool quiet = listed == h->listed_seen;
   h->listed_seen = listed;
   if (hk != 0 && hd != 0) return fail(h, SWIM_EDEVICE, "speculative batch: a gossip halt and a diff-halt");
@@ -95,7 +96,7 @@ int spec_batch(swim_handle* h, Step& s) {
     const uint32_t kd = hd - 1u;
     if (!elide || kd < k0 || kd >= k + (nb - i) || prof_timed(h, kd))
       return fail(h, SWIM_EDEVICE, "speculative batch: bad diff-halt tick");
-    HIPCK(hipMemsetAsync(d.halt + 1, 0, 4, h->stream));
+    HIPCK(hipMemsetAsync(&d.halt[HALT_DIFF], 0, 4, h->stream));
     launch_diff_listed(d, kd, h->stream);
     h->diff_elided += elided(k0, kd);
     h->diff_halts++;
@@ -108,7 +109,7 @@ int spec_batch(swim_handle* h, Step& s) {
   }
   const uint32_t kh = hk - 1u;  // member(kh) ran; the launches after it returned at once
   if (kh < k || kh >= k + (nb - i)) return fail(h, SWIM_EDEVICE, "speculative batch: bad halt tick");
-  HIPCK(hipMemsetAsync(d.halt, 0, 4, h->stream));
+  HIPCK(hipMemsetAsync(&d.halt[HALT_GOSSIP], 0, 4, h->stream));
   const uint32_t ih = i + (kh - k);
   // a speculative member launch publishes no flag (tick_flag): the slots in use after member(kh) are read here, so
   // the first gossip plane after an idle stretch gets the same capacity check as every other one (grow_caps); the
@@ -118,8 +119,8 @@ int spec_batch(swim_handle* h, Step& s) {
     HIPCK(hipMemcpyAsync(&top, d.free_top, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
     const uint32_t used = (uint32_t)((int32_t)d.SPR - top);
-    h->hflag[0] = used;
-    HIPCK(hipMemcpyAsync(d.hsh, &used, 4, hipMemcpyHostToDevice, h->stream));
+    h->hflag[HF_USED] = used;
+    HIPCK(hipMemcpyAsync(&d.hsh[HSH_USED], &used, 4, hipMemcpyHostToDevice, h->stream));
     int gr;
     if ((gr = grow_caps(h)) != SWIM_OK) return gr;
   }
@@ -142,20 +143,20 @@ int tick_one_gpu(swim_handle* h, Step& s) {
   // SYNC diff(k) was queued in the previous iteration, except for the first tick of this call
   if (s.need_front) launch_diff(d, k, h->stream, te);
   launch_member(d, k, h->stream, te, false, h->gossip_ran && !d.fastp4);
-  const bool nosync = (d.exp & 256) != 0;  // timing experiment: no per-tick event (gossip plane never launched)
+  const bool nosync = (d.exp & EXP_NO_EVENT) != 0;  // timing experiment: no per-tick event (gossip plane never launched)
   if (!nosync) HIPCK(hipEventRecord(h->ev_member, h->stream));
   const bool pipe = i + 1 < s.n && !h->no_pipe;
   if (pipe) launch_diff(d, k + 1, h->stream, events_of(h, k + 1ull, i + 1));  // overlaps the wait
   s.need_front = !pipe;
   if (!nosync) HIPCK(hipEventSynchronize(h->ev_member));  // (a spin wait measured the same here: diff(k+1) hides the wake-up)
-  h->gossip_idle = !nosync && h->hflag[0] == 0;
+  h->gossip_idle = !nosync && h->hflag[HF_USED] == 0;
   if (!nosync && !h->gossip_idle) {  // slots, rings and receipt lists sized up before they can overflow
     int gr;
     if ((gr = grow_caps(h)) != SWIM_OK) return gr;
   }
-  h->gossip_ran = !nosync && (h->hflag[0] != 0 || h->no_skip);
+  h->gossip_ran = !nosync && (h->hflag[HF_USED] != 0 || h->no_skip);
   if (nosync) {
-  } else if (h->hflag[0] != 0 || h->no_skip) {
+  } else if (h->hflag[HF_USED] != 0 || h->no_skip) {
     launch_gossip(d, k, h->stream, te);
     int sr;
     if (h->stats && (sr = stats_dump(h, k)) != SWIM_OK) return sr;
@@ -200,9 +201,9 @@ int shard_spec_batch(swim_handle* h, Step& s) {
     if ((xr = exchange_inline(h, d.xa_recv, d.XA_PEER, d.xa_scnt, d.xa_rcnt, true)) != SWIM_OK) return xr;
     launch_tick_b(d, kj, h->stream, tj, false, true);
   }
-  HIPCK(hipMemcpyAsync((void*)(h->hflag + 1), d.halt, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipMemcpyAsync((void*)(h->hflag + HF_SHARD_HALT), &d.halt[HALT_GOSSIP], 4, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
-  const uint32_t hk = h->hflag[1];
+  const uint32_t hk = h->hflag[HF_SHARD_HALT];
   if (hk == 0) {
     h->tick += nb - i;
     s.i = nb;
@@ -210,7 +211,7 @@ int shard_spec_batch(swim_handle* h, Step& s) {
   }
   const uint32_t kh = hk - 1u;  // tick kh ran up to its inline exchange; the launches after that returned at once
   if (kh < k || kh >= k + (nb - i)) return fail(h, SWIM_EDEVICE, "speculative sharded batch: bad halt tick");
-  HIPCK(hipMemsetAsync(d.halt, 0, 4, h->stream));
+  HIPCK(hipMemsetAsync(&d.halt[HALT_GOSSIP], 0, 4, h->stream));
   const uint32_t ih = i + (kh - k);
   if ((xr = exchange_rest(h, d.xa_send, d.xa_recv, d.XA_PEER)) != SWIM_OK) return xr;
   if ((xr = shard_tick_rest(h, kh, events_of(h, kh, ih))) != SWIM_OK) return xr;
@@ -243,9 +244,9 @@ int shard_tick(swim_handle* h, Step& s) {
 // counters are read back only when the lister flagged a streamed chunk (never in a cluster whose rows are all clean).
 static int rebase_check(swim_handle* h) {
   const Dev& d = h->d;
-  if (h->tick < h->next_rebase || !h->hflag[7]) return SWIM_OK;
+  if (h->tick < h->next_rebase || !h->hflag[HF_STREAMED]) return SWIM_OK;
   h->next_rebase = h->tick + h->rb_int;
-  h->hflag[7] = 0;
+  h->hflag[HF_STREAMED] = 0;
   std::vector<unsigned long long> c(3ull * d.NCHUNK);  // chunk q's streamed, differed, sender: member q's record
   HIPCK(hipMemcpy2DAsync(c.data(), 24, (const char*)d.ms + offsetof(MS, cstat), sizeof(MS), 24, d.NCHUNK, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
@@ -292,9 +293,9 @@ extern "C" int swim_step(swim_handle* h, uint32_t n) {
     if (rc != SWIM_OK) return rc;
   }
   rc = check_err(h);
-  if (rc == SWIM_OK && (d.exp & (16 | 128))) rc = exp_dump_member_cycles(h);
-  if (rc == SWIM_OK && (d.exp & 512)) rc = exp_dump_wave_clock(h);
-  if (rc == SWIM_OK && (d.exp & 4)) rc = exp_dump_gossip_work(h);
+  if (rc == SWIM_OK && (d.exp & EXP_CYCLES)) rc = exp_dump_member_cycles(h);
+  if (rc == SWIM_OK && (d.exp & EXP_WAVE_CLOCK)) rc = exp_dump_wave_clock(h);
+  if (rc == SWIM_OK && (d.exp & EXP_GOSSIP_WORK)) rc = exp_dump_gossip_work(h);
   if (rc == SWIM_OK) rc = prof_accumulate(h, first, n);
   return rc;
 }
