@@ -7,6 +7,7 @@
 
 #include "../../include/swimhip_wire.h"
 #include "../../include/swimhip_debug.h"
+#include "../../include/swimhip_census.h"
 #include "group.h"
 
 using namespace swim;
@@ -488,6 +489,127 @@ int swim_read_row(swim_handle* h, uint32_t obs, uint64_t* out, size_t cap) {
   HIPCK(hipMemcpy(a.data(), h->d.rowa + lidx(h->d, obs) * h->d.NS, 4ull * h->d.N, hipMemcpyDeviceToHost));
   for (uint32_t s = 0; s < h->d.N; ++s) out[s] = (k[s] & 3u) == ST_ABSENT ? 0 : rec_join(k[s], a[s]);
   return SWIM_OK;
+}
+
+// the shards' partial censuses combined (swimhip_census.h): counts add, key ranges widen, by_observer rows are disjoint
+static int group_census(swim_handle* h, swim_census* c) {
+  const size_t N = h->cfg.n_members;
+  if (h->grp->slots) {  // slot-sharded: every shard holds every view
+    swim_handle* s = h->grp->shards[0];
+    hipSetDevice((int)s->cfg.device);
+    const int rc = swim_view_census(s, c);
+    return rc == SWIM_OK ? rc : fail(h, rc, "shard 0: " + s->err);
+  }
+  std::vector<uint32_t> bs(c->by_subject ? 4 * N : 0), bo(c->by_observer ? 4 * N : 0), mn(c->key_min ? N : 0),
+      mx(c->key_max ? N : 0);
+  if (c->by_subject) std::fill(c->by_subject, c->by_subject + 4 * N, 0u);
+  if (c->by_observer) std::fill(c->by_observer, c->by_observer + 4 * N, 0u);
+  if (c->key_min) std::fill(c->key_min, c->key_min + N, 0xFFFFFFFFu);
+  if (c->key_max) std::fill(c->key_max, c->key_max + N, 0u);
+  swim_census p = *c, sum = *c;
+  p.by_subject = c->by_subject ? bs.data() : nullptr;
+  p.by_observer = c->by_observer ? bo.data() : nullptr;
+  p.key_min = c->key_min ? mn.data() : nullptr;
+  p.key_max = c->key_max ? mx.data() : nullptr;
+  sum.n_observers = sum.bytes_read = 0;
+  std::fill(sum.records, sum.records + 4, 0ull);
+  const int rc = group_all(h, [&](swim_handle* s) {
+    const int r = swim_view_census(s, &p);
+    if (r != SWIM_OK) return r;
+    for (size_t i = 0; i < bs.size(); ++i) c->by_subject[i] += bs[i];
+    for (size_t i = 0; i < bo.size(); ++i) c->by_observer[i] += bo[i];
+    for (size_t i = 0; i < mn.size(); ++i) c->key_min[i] = std::min(c->key_min[i], mn[i]);
+    for (size_t i = 0; i < mx.size(); ++i) c->key_max[i] = std::max(c->key_max[i], mx[i]);
+    sum.tick = p.tick;
+    sum.path = p.path;
+    sum.n_observers += p.n_observers;
+    sum.bytes_read += p.bytes_read;
+    for (int st = 0; st < 4; ++st) sum.records[st] += p.records[st];
+    return r;
+  });
+  c->tick = sum.tick;
+  c->path = sum.path;
+  c->n_observers = sum.n_observers;
+  c->bytes_read = sum.bytes_read;
+  std::copy(sum.records, sum.records + 4, c->records);
+  std::fill(c->reserved, c->reserved + 3, 0u);
+  return rc;
+}
+
+int swim_view_census(swim_handle* h, swim_census* c) {
+  if (!h || !c) return SWIM_EINVAL;
+  if (h->grp) return group_census(h, c);
+  const Dev& d = h->d;
+  const size_t N = d.N;
+  const uint32_t now = (uint32_t)h->tick;
+  c->tick = h->tick;
+  c->n_observers = c->bytes_read = 0;
+  std::fill(c->records, c->records + 4, 0ull);
+  std::fill(c->reserved, c->reserved + 3, 0u);
+  HIPCK(hipStreamSynchronize(h->stream));
+  if (d.implicit) {  // every row is the PRECONVERGED row (PRE_REC): nothing to read
+    c->path = SWIM_CENSUS_PATH_IMPLICIT;
+    std::vector<uint32_t> dt(N);
+    if (!c->observers) HIPCK(hipMemcpy(dt.data(), d.dead_tick, 4 * N, hipMemcpyDeviceToHost));
+    if (c->by_observer) std::fill(c->by_observer, c->by_observer + 4 * N, 0u);
+    for (uint32_t m = d.lo; m < d.hi; ++m)
+      if (c->observers ? c->observers[m] != 0 : dt[m] > now) {
+        ++c->n_observers;
+        if (c->by_observer) c->by_observer[4ull * m + ST_ALIVE] = d.N;
+      }
+    const uint32_t n = (uint32_t)c->n_observers, key = key32(PRE_REC);
+    c->records[ST_ALIVE] = c->n_observers * N;
+    for (size_t s = 0; s < N; ++s) {
+      if (c->by_subject) {
+        std::fill(c->by_subject + 4 * s, c->by_subject + 4 * s + 4, 0u);
+        c->by_subject[4 * s + ST_ALIVE] = n;
+      }
+      if (c->key_min) c->key_min[s] = n ? key : 0xFFFFFFFFu;
+      if (c->key_max) c->key_max[s] = n ? key : 0u;
+    }
+    return check_err(h);
+  }
+  c->path = d.rowk8 ? SWIM_CENSUS_PATH_KEY8 : SWIM_CENSUS_PATH_KEY32;
+  // scratch of this call: the totals, the caller's mask, then the requested outputs (key_min and key_max together)
+  const bool keys = c->key_min || c->key_max;
+  const size_t o_sel = 64, o_bs = o_sel + ((N + 63) & ~(size_t)63), o_bo = o_bs + (c->by_subject ? 16 * N : 0),
+               o_mn = o_bo + (c->by_observer ? 16 * N : 0), o_mx = o_mn + (keys ? 4 * N : 0),
+               bytes = o_mx + (keys ? 4 * N : 0);
+  static_assert(CT_N * sizeof(unsigned long long) <= 64, "the totals fit the scratch header");
+  static_assert(SWIM_CENSUS_TILE_ROWS == CENSUS_ROWS && SWIM_CENSUS_TILE_COLS == CENSUS_COLS, "the documented tile");
+  char* buf = nullptr;
+  HIPCK(hipMalloc(&buf, bytes));
+  CensusOut o{};
+  o.tot = (unsigned long long*)buf;
+  if (c->by_subject) o.by_subject = (uint32_t*)(buf + o_bs);
+  if (c->by_observer) o.by_observer = (uint32_t*)(buf + o_bo);
+  if (keys) o.key_min = (uint32_t*)(buf + o_mn), o.key_max = (uint32_t*)(buf + o_mx);
+  unsigned long long tot[CT_N] = {};
+  hipError_t e = hipMemsetAsync(buf, 0, bytes, h->stream);
+  if (e == hipSuccess && keys) e = hipMemsetAsync(o.key_min, 0xFF, 4 * N, h->stream);
+  if (e == hipSuccess && c->observers) e = h2d(h->stream, buf + o_sel, c->observers, N);
+  if (e == hipSuccess) {
+    launch_census(d, c->observers ? (const uint8_t*)(buf + o_sel) : nullptr, now, o, h->stream);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = hipMemcpy(tot, o.tot, sizeof(tot), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && c->by_subject) e = hipMemcpy(c->by_subject, o.by_subject, 16 * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && c->by_observer) e = hipMemcpy(c->by_observer, o.by_observer, 16 * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && c->key_min) e = hipMemcpy(c->key_min, o.key_min, 4 * N, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && c->key_max) e = hipMemcpy(c->key_max, o.key_max, 4 * N, hipMemcpyDeviceToHost);
+  hipFree(buf);
+  HIPCK(e);
+  // the kernel counts ABSENT, SUSPECT and DEAD; ALIVE is what remains of the rows counted
+  c->n_observers = tot[CT_ROWS];
+  for (uint32_t st = 0; st < 4; ++st) c->records[st] = tot[CT_ST + st];
+  c->records[ST_ALIVE] = tot[CT_ROWS] * N - tot[CT_ST + ST_ABSENT] - tot[CT_ST + ST_SUSPECT] - tot[CT_ST + ST_DEAD];
+  for (size_t s = 0; c->by_subject && s < N; ++s) {
+    uint32_t* b = c->by_subject + 4 * s;
+    b[ST_ALIVE] = (uint32_t)tot[CT_ROWS] - b[ST_ABSENT] - b[ST_SUSPECT] - b[ST_DEAD];
+  }
+  c->bytes_read = tot[CT_ROWS] * N * (d.rowk8 ? 1u : 4u) + 4 * tot[CT_ESC];
+  return check_err(h);
 }
 
 int swim_export_sync_frame(swim_handle* h, uint32_t obs, uint32_t kind, uint8_t* buf, size_t cap, size_t* len) {

@@ -535,6 +535,18 @@ void launch_key_set(const Dev& d, uint32_t m, uint32_t s, uint32_t key, void* st
 // row's chunk counted into *viol, the set bits of the masks summed into *ndirty; ref: [NCHUNK] scratch
 void launch_dirty_check(const Dev& d, uint32_t* viol, uint32_t* ndirty, uint32_t* ref, void* stream);
 void launch_dbg_holders(const Dev& d, uint32_t first, uint32_t n, uint32_t* out, void* stream);  // swim_debug_holders
+// census.hip (swim_view_census, stored tables): one read-only pass over the key plane (its 8-bit shadow when the handle
+// has one) that counts the records of the selected rows of this shard by subject and by observer. Selected: sel[m] != 0
+// (sel: [N] bytes), or with sel null the members running at tick now. Every output may be null and is zero-filled
+// (key_min: 0xFF bytes) by the caller: by_subject / by_observer [4 N] (by_subject's ALIVE column is left to the host:
+// counted rows less the other three), key_min / key_max [N], tot [CT_N] (CensusTot)
+enum CensusTot { CT_ROWS = 0, CT_ST = 1, CT_ESC = 5, CT_N = 6 };  // rows counted, records by status, escaped subjects
+constexpr uint32_t CENSUS_ROWS = 128, CENSUS_COLS = 4096;  // a block's tile: observers x subjects (census.hip)
+struct CensusOut {
+  uint32_t *by_subject, *by_observer, *key_min, *key_max;
+  unsigned long long* tot;
+};
+void launch_census(const Dev& d, const uint8_t* sel, uint32_t now, const CensusOut& o, void* stream);
 // launchers one kernel file calls in another
 static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 void launch_gossip_send(const Dev& d, uint32_t k, hipStream_t st, const TickEvents* prof);  // gossip.hip

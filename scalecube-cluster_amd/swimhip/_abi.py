@@ -180,6 +180,41 @@ SHARD_SIGNATURES = {
 }
 
 
+# include/swimhip_census.h (the cluster-wide view census; exported by libswimhip only, not by the oracle)
+CENSUS_PATH_IMPLICIT, CENSUS_PATH_KEY8, CENSUS_PATH_KEY32 = 0, 1, 2
+CENSUS_TILE_ROWS, CENSUS_TILE_COLS = 128, 4096  # the kernel's tile: observers x subjects (SWIM_CENSUS_TILE_*)
+
+
+class SwimCensus(C.Structure):
+    _fields_ = [
+        ("observers", C.POINTER(C.c_uint8)),
+        ("by_subject", _U32P),
+        ("by_observer", _U32P),
+        ("key_min", _U32P),
+        ("key_max", _U32P),
+        ("tick", C.c_uint64),
+        ("n_observers", C.c_uint64),
+        ("records", C.c_uint64 * 4),
+        ("bytes_read", C.c_uint64),
+        ("path", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+CENSUS_SIGNATURES = {
+    "swim_view_census": (C.c_int, [_H, C.POINTER(SwimCensus)]),
+}
+
+
+def bind_census(lib):
+    """Attach the census entry point (engine library only)."""
+    for name, (res, args) in CENSUS_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 # include/swimhip_selftest.h (known-answer surface; exported by libswimhip and by the oracle)
 SELFTEST_OVERRIDES, SELFTEST_PHILOX, SELFTEST_CLUSTER_MATH, SELFTEST_LOSS_ROLL = 0, 1, 2, 3
 SELFTEST_SIGNATURES = {

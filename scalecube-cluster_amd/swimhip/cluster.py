@@ -248,6 +248,14 @@ class SimulatedCluster:
                  "swim_state_hash")
         return out.reshape(self.n, _abi.HASH_WORDS)
 
+    def census(self, observers=None, by_subject=True, by_observer=True, keys=True):
+        """The view census over every running member's table, or over the observers flagged in `observers` (n flags):
+        a swimhip.census.ViewCensus (include/swimhip_census.h; engine only). Outputs switched off stay None."""
+        from .census import view_census
+        rc, out = view_census(self.lib, self._h, self.n, observers, by_subject, by_observer, keys)
+        self._ck(rc, "swim_view_census")
+        return out
+
     def counters(self):
         c = _abi.SwimCounters()
         self._ck(self.lib.swim_counters_get(self._h, C.byref(c)), "swim_counters_get")

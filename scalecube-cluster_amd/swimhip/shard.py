@@ -329,6 +329,14 @@ class ThreadShardGroup:
                 h += s.state_hash()  # disjoint observer rows; the rest are zero
         return h
 
+    def census(self, observers=None, by_subject=True, by_observer=True, keys=True):
+        """The whole cluster's view census: the row shards' partial ones combined (swimhip.census.combine); slot shards
+        hold every view replicated, so one shard's."""
+        from .census import combine
+        if self.slots:
+            return self.shards[0].census(observers, by_subject, by_observer, keys)
+        return combine([s.census(observers, by_subject, by_observer, keys) for s in self.shards])
+
     def counters(self):
         cs = [s.counters() for s in self.shards]
         return {k: (sum(c[k] for c in cs) if k != "tick" else cs[0][k]) for k in cs[0]}
