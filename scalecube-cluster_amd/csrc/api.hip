@@ -984,7 +984,8 @@ int swimdbg_send_log(swim_handle* h, uint32_t* out, size_t cap, size_t* n) {
   return SWIM_OK;
 }
 
-// debugging aid (not part of the ABI header): the scalar fields folded into the "misc" state-hash word
+// debugging aid (not part of the ABI header): the scalar fields folded into the "misc" state-hash word (out[0..5]),
+// then the member's pending ping paths and subscriptions (out[6], out[7]: MS::npath, MS::nsub)
 int swimdbg_scalars(swim_handle* h, uint32_t m, uint64_t* out) {
   if (!h || !owns(h, m)) return SWIM_EINVAL;
   HIPCK(hipStreamSynchronize(h->stream));
@@ -994,6 +995,8 @@ int swimdbg_scalars(swim_handle* h, uint32_t m, uint64_t* out) {
   HIPCK(hipMemcpy(&ns, h->d.nextSync + m, 4, hipMemcpyDeviceToHost));
   const uint32_t v[6] = {ms.cidCnt, ms.syncSeq, ms.gCounter, ns, ms.fdPeriod, ms.gPeriod};
   for (int i = 0; i < 6; ++i) out[i] = (i == 3 && v[i] == NEVER) ? ~0ull : v[i];
+  out[6] = ms.npath;
+  out[7] = ms.nsub;
   return SWIM_OK;
 }
 

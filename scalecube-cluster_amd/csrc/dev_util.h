@@ -263,6 +263,38 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t* ctr) {
   return base + rank;
 }
 
+// the wave's sum (u32, and u64 as two 32-bit shuffles per step) and minimum of a value every lane holds
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, o), hi = __shfl_xor((uint32_t)(v >> 32), o);
+    v += ((unsigned long long)hi << 32) | lo;
+  }
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor(v, o));
+  return v;
+}
+
+// a member kernel's eight op counters (engine.h C_*) summed across the wave first, then one atomic each into the
+// block's shard of Dev::ctr_sh: 10^4 pingers per tick adding to one word would serialise on that address
+template <typename T>
+__device__ __forceinline__ void ctr_wave_add(const Dev& d, const T (&c)[8], uint32_t lane) {
+  unsigned long long* cs = d.ctr_sh + (size_t)(blockIdx.x % CSH) * CSTRIDE;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const unsigned long long v = wave_sum((unsigned long long)c[i]);
+    if (lane == 0 && v) atomicAdd(&cs[i], v);
+  }
+}
+
 // reserve n entries per lane on a shared counter with ONE atomic per wave; every lane of the wave must call it
 // (inactive work passes n = 0). Returns the lane's first index.
 __device__ __forceinline__ uint32_t wave_reserve(uint32_t* ctr, uint32_t n) {
@@ -304,7 +336,7 @@ __device__ __forceinline__ uint32_t block_reserve(uint32_t* ctr, uint32_t n, uin
 }
 
 // A receiver with several SYNC / SYNC_ACK payloads in one tick reads the later ones' records for the subjects an
-// earlier one changed (member.hip, merge_payload), after their senders may have written their live rows again:
+// earlier one changed (member_proto.h, merge_payload), after their senders may have written their live rows again:
 // such a live-row payload gets an arena row that k_sync_diff fills with its keys. A lost CAS race wastes a row.
 __device__ __forceinline__ void pin_msg(const Dev& d, uint32_t b, uint32_t j) {
   uint32_t* p = &d.msgs[b][j].pin;
@@ -448,6 +480,30 @@ __device__ __forceinline__ void slot_create(const Dev& d, uint32_t g, uint32_t m
   atomicOr(&hrow(d, m)[g >> 6], bit);
   ring(d, m)[pos & (d.BCAP - 1)] = rg_entry(g, rounds_before(d, m, k));
   if (pos + 1u - d.rhead[m] > d.BCAP) set_err(d, E_RING);
+}
+
+// createAndPutGossip (GossipProtocolImpl.java:163-169): gossip slot g becomes a new gossip held by member m since tick
+// k (slot_create: slot tables and the creator's holder state, ring position pos); with row shards it is replicated on
+// the other shards from exchange A
+__device__ __forceinline__ void slot_init(const Dev& d, uint32_t g, uint32_t m, uint32_t k, uint64_t gid, uint32_t subj,
+                                          uint64_t key, uint32_t pos) {
+  slot_create(d, g, m, k, gid, subj, key, pos);
+  if (d.W > 1) {
+    uint32_t i = atomicAdd(&d.xn[0], 1u);
+    if (i >= d.NSCAP) {
+      set_err(d, E_XCAP);
+      return;
+    }
+    uint32_t* r = d.ns_rec + (size_t)i * NSW;
+    r[0] = g;
+    r[1] = (uint32_t)gid;
+    r[2] = (uint32_t)(gid >> 32);
+    r[3] = subj;
+    r[4] = k;
+    r[5] = (uint32_t)key;
+    r[6] = (uint32_t)(key >> 32);
+    r[7] = m;
+  }
 }
 
 // end of a sharded tick (W > 1): the same resets, plus the exchange counters (one block)

@@ -28,11 +28,11 @@ constexpr uint32_t CH = 2048;  // subjects per SYNC-diff work item (256 threads 
 constexpr uint32_t MCH = 1024;  // subjects per candidate-list segment (chunk_meta): one wave of 16-bit keys
 constexpr uint32_t TRK = 16;   // subjects written in one tick's P1 that are re-checked against later payloads (sorted list)
 constexpr uint32_t TRKL = 64;  // of them listed per member for clearing its written-subject bitmap (more: the whole row)
-// deferred copy-on-write (member.hip cow): row writes logged per member and tick while a snapshot is open, open
+// deferred copy-on-write (member_state.h cow): row writes logged per member and tick while a snapshot is open, open
 // snapshots per member, deferred snapshots per k_member_tick block
 constexpr uint32_t ULOG = 1024, CREQ = 4, CWMAX = 32;  // ULOG: the largest undo log (Dev::ULOGC is the stride in use)
 constexpr uint32_t SPQ = 32;  // gossips a member creates in one tick before their slots are taken together
-constexpr uint32_t KP = 64;   // FD-list inserts of one member's tick applied together (member.hip fd_flush)
+constexpr uint32_t KP = 64;   // FD-list inserts of one member's tick applied together (member_proto.h fd_flush)
 constexpr uint32_t MQ = 16;   // inbound SYNC messages of one tick sorted in registers (more: selected by list walks)
 constexpr uint32_t SORT_MAX = 4096;  // receipts of one member and tick sorted in LDS at once (more: runs + merges)
 
@@ -333,12 +333,12 @@ struct Dev {
   uint32_t* next_evt; // [N] earliest tick at which a pending path / subscription / fetch needs the member
   uint32_t* mdone;  // finished k_member_tick blocks this tick (the last one runs the end-of-tick resets)
   uint32_t* halt;  // [HALT_WORDS] the speculative batches' halt words (spec.h): ctr_sh + SH_HALT
-  uint32_t* trk;    // [NL][TRKL] per receiver: subjects its row changed earlier in this tick's P1 (member.hip)
+  uint32_t* trk;    // [NL][TRKL] per receiver: subjects its row changed earlier in this tick's P1 (member_state.h row_put)
   unsigned long long* tbm;  // [NL][NW] the same subjects as a bitmap (zero between ticks): merged in subject order
   uint32_t NW;       // u64 words per bitmap row ((N + 63) / 64; no SYNC with implicit views: 0)
   uint32_t* ulog;   // [NL][ULOGC][2] per member: (subject, old key) of its row writes this tick after a SYNC send
   uint32_t ULOGC;   // undo-log entries per member (1024 up to 65 536 members, 256 above; ulog_cap <= ULOGC)
-  uint32_t* spq;    // [NL][SPQ][8] per member: gossips created this tick, waiting for their slots (member.hip)
+  uint32_t* spq;    // [NL][SPQ][8] per member: gossips created this tick, waiting for their slots (member_proto.h spread)
   uint32_t* fpend;  // [NL][KP][2] per member: this tick's pending FD-list inserts (subject, final position)
   uint32_t* chunk_meta;                      // [MSGCAP][NMETA][2] (pool offset, count) per MCH subjects
   uint64_t* pool;                            // candidate (subject << 34 | key)

@@ -6,9 +6,12 @@
 //   diag.hip      SWIM_STATS / SWIM_EXP dumps, profile events
 //   group.hip     swim_config.n_gpus > 1: one handle over several shard handles
 //   api.hip       the other extern "C" entry points: fault injection, readback
-// The device side (engine.h, spec.h, dev_util.h): member.hip (member control), sync_diff.hip (SYNC diff and its lister),
-// sync_delay.hip (delayed-SYNC store), route.hip (receipt routing), gossip.hip (gossip data plane), shard.hip (row-shard
-// pack / unpack), kernels.hip (initialisation, state hashes, the tick launchers).
+// The device side (engine.h, spec.h, dev_util.h): member.hip (member control: triage, phases, k_member_tick_t) over
+// member_state.h (a member's state, row writes, SYNC sends) and member_proto.h (the protocol handlers), inbox.hip
+// (k_inbox_apply: P4 of a parked member on one wave), user_gossip.hip (host-queued gossips, churn), sync_diff.hip (SYNC
+// diff and its lister), sync_delay.hip (delayed-SYNC store), route.hip (receipt routing), gossip.hip (gossip data
+// plane), shard.hip (row-shard pack / unpack), kernels.hip (initialisation, state hashes, the tick launchers; the
+// member kernels it launches are declared in member_kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

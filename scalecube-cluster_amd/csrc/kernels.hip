@@ -4,13 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include "dev_util.h"
+#include "member_kernels.h"
 
 namespace swim {
 
-enum : uint32_t { BODY_FULL = 0, BODY_SPLIT = 1, BODY_RESUME = 2 };  // member.hip
-template <uint32_t MODE>
-__global__ void k_member_tick_t(const Dev* __restrict__ dp, uint32_t k, uint32_t flag);  // member.hip
-__global__ void k_inbox_apply(const Dev* __restrict__ dp, uint32_t k);  // member.hip
 __global__ void k_pack_all(Dev d, uint32_t b, uint32_t spec);  // shard.hip
 __global__ void k_unpack_a(Dev d, uint32_t k, uint32_t end, uint32_t spec);
 __global__ void k_pack_b(Dev d);

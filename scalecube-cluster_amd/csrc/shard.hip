@@ -275,14 +275,14 @@ __global__ void __launch_bounds__(256) k_unpack_a(Dev d, uint32_t k, uint32_t en
     const uint8_t* E = (const uint8_t*)(RR + (size_t)nround * RRW);
     const uint64_t SE = sync_entry_bytes(d);
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
-    for (uint32_t i = tid; i < nslot; i += nth) {  // spread -> createAndPutGossip at the origin (member.hip)
+    for (uint32_t i = tid; i < nslot; i += nth) {  // spread -> createAndPutGossip at the origin (member_proto.h)
       const uint32_t* r = S + (size_t)i * NSW;
       const uint32_t g = r[0], origin = r[7];
       slot_create(d, g, origin, r[4], (uint64_t)r[1] | ((uint64_t)r[2] << 32), r[3], (uint64_t)r[5] | ((uint64_t)r[6] << 32),
                   atomicAdd(&d.rtail[origin], 1u));
       atomicAdd(&d.held[origin], 1u);
     }
-    for (uint32_t i = tid; i < nround; i += nth) {  // do_spread_gossip at the sender (member.hip)
+    for (uint32_t i = tid; i < nround; i += nth) {  // do_spread_gossip at the sender (member_proto.h)
       const uint32_t* r = RR + (size_t)i * RRW;
       uint32_t m = r[0], cnt = r[1];
       d.tround[m] = 1;

@@ -47,7 +47,7 @@ def _explain(o, e, member):
         for c in (o, e):
             fn = c.lib.swimdbg_scalars
             fn.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
-            out = (C.c_uint64 * 6)()
+            out = (C.c_uint64 * 8)()  # (the engine adds its pending paths and subscriptions: test_gpu_inbox.py)
             fn(c._h, member, out)
             vals.append(list(out))
         sc = "scalars oracle/engine " + ", ".join(f"{n} {a}/{b}" for n, a, b in zip(names, *vals)) + "; "

@@ -1,4 +1,4 @@
-"""P4 on a wave per member (member.hip k_inbox_apply) against the golden fixtures.
+"""P4 on a wave per member (inbox.hip k_inbox_apply) against the golden fixtures.
 
 In a tick after a gossip plane, k_member_tick parks every member with at least Dev::hv routed gossip receipts before
 P4; k_inbox_apply then runs each parked member's receipts on a whole wave, 64 at a time (onMembershipGossip ->
@@ -64,5 +64,49 @@ def test_inbox_waves_refutations_and_leaves(oracle, engine, monkeypatch, seed):
         c.spread_gossip(5, 77)
         c.spread_gossip(5, 78)
     run_lockstep(o, e, 400, 50, "kill + leave + user gossips")
+    o.close()
+    e.close()
+
+
+def _pending(c, members):
+    """The largest number of pending ping paths and of pending subscriptions any engine member holds now (MS::npath,
+    MS::nsub: words 6 and 7 of the swimdbg_scalars debug call)."""
+    import ctypes as C
+    fn = c.lib.swimdbg_scalars
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 8)()
+    npath = nsub = 0
+    for m in range(members):
+        assert fn(c._h, m, out) == 0
+        npath, nsub = max(npath, int(out[6])), max(nsub, int(out[7]))
+    return npath, nsub
+
+
+def test_parked_member_with_many_pending_requests(oracle, engine, monkeypatch):
+    """The resumed launch of a parked member (P5 and P6 after k_inbox_apply) recomputes the member's next event from
+    memory: the first four ping paths and subscriptions loaded together, the rest in a loop. Mean link delays of
+    400 ms (4 ticks per hop) against the 500 ms ping timeout and the 1 s ping interval keep the hops of one period's
+    ping-req round (3 helpers, 4 hops each) in flight while the next period's ping starts, so members hold more than
+    four of either; incarnation bumps keep gossip receipts flowing, and with hv=1 every receipt parks its member."""
+    n = 40
+    cfg = SimConfig(n_members=n, cluster=ClusterConfig(syncInterval=3000), record_events=True, delay_cap_ms=400,
+                    gossip_slot_cap=8192)
+    monkeypatch.setenv("SWIM_CAPS", "hv=1")
+    o, e = pair(oracle, engine, cfg)
+    monkeypatch.delenv("SWIM_CAPS")
+    for c in (o, e):
+        c.set_default_link_settings(5, 400)
+    most_paths = most_subs = 0
+    for r in range(30):  # 300 ticks, checked every 10; a few bumps every 50
+        if r % 5 == 0:
+            for c in (o, e):
+                for m in range(r % 7, n, 9):
+                    c.update_incarnation(m)
+        run_lockstep(o, e, 10, 10, f"overlapping ping rounds, check {r}", events=False)
+        p, s = _pending(e, n)
+        most_paths, most_subs = max(most_paths, p), max(most_subs, s)
+    assert o.events() == e.events()
+    print(f"most pending ping paths {most_paths}, subscriptions {most_subs}")
+    assert most_paths > 4 or most_subs > 4, (most_paths, most_subs)
     o.close()
     e.close()

@@ -17,9 +17,9 @@ o, e = SimulatedCluster(_abi.load("oracle/liboracle_swimref.so"), cfg), Simulate
 def sc(c):
     fn = c.lib.swimdbg_scalars
     fn.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
-    out = (C.c_uint64 * 6)()
+    out = (C.c_uint64 * 8)()  # (the engine also writes its pending paths and subscriptions, words 6 and 7)
     fn(c._h, mem, out)
-    return list(out)
+    return list(out)[:6]
 
 
 orig = parity_util.run_lockstep
