@@ -101,6 +101,71 @@ int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n);
  * (0 in a correct engine). One pass over the key plane. */
 int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
 
+/* Known-answer surface of the device primitives the per-tick kernels are made of (no handle): the engine's own scan,
+ * segmented sort, receipt routing, ring move and inline device helpers run on caller data, in the block shape the
+ * engine launches them in (256 threads), so a test can compare each with a plain reference at the sizes and lane masks
+ * where such code goes wrong. Every buffer is allocated by the call and freed before it returns. Sizes, offsets and
+ * indices are checked on the host first: anything the layouts below do not allow is SWIM_EINVAL before any launch.
+ * `in` and `out` are 8-byte aligned arrays of 32-bit words (u64 = two words, low first) in the order listed; `out` is
+ * also read where marked in/out (the caller's sentinels or preset bits). T = 256 * blocks threads.
+ *
+ * SCAN       params n (1..2^20)                        in  v[n]
+ *            launch_scan                               out x[n + 64] in/out (words at and past n are not written)
+ * SEG_SORT   params total, nmem, nlist, run, fb        in  key u64[total], val[total], off[nmem], cnt[nmem], sg[nlist]
+ *            k_seg_sort, 1024 blocks; run a power of   out merges u64 (FB_SORT_MERGE; fb = 0: a null counter), key
+ *            two in 2..4096; off + cnt <= total            u64[total], val[total]
+ * ROUTING    params N, RCAP, rc_n, SLOTS, sort_cap, fb in  rc_raw u64[min(rc_n, RCAP)] (member << 32 | slot), slot_gid
+ *            launch_receipt_routing on a zeroed Dev        u64[SLOTS]
+ *                                                      out rc_key u64[RCAP] in/out, merges u64, rc_slot[RCAP] in/out,
+ *                                                          rc_off[N], rc_cnt[N], sg_list[N] in/out, nsg, 0
+ * WAVE       params sub, blocks (1..64)                in  a[3][T]
+ *            sub APPEND: lanes with a[0] != 0 call     out r[3][T] in/out, ctr[4] in/out (ctr[0] is the counter)
+ *            wave_append; WAVE_RESERVE / BLOCK_RESERVE: every thread reserves a[0] (block: a[0], a[1], a[2] in three
+ *            calls on one LDS scratch); SUM32 / MIN32: wave_sum / wave_min of a[0]; SUM64: of a[0] | a[1] << 32 into
+ *            r[0], r[1]
+ * DIRTY      params wave, blocks (1..64), MW (1..3)    in  a[3][T]
+ *            wave = 0: thread t owns mask row t and    out mask u64[rows][MW] in/out (rows = T, or T / 64)
+ *            calls dirty_mark for each a[j][t] != 0xFFFFFFFF; wave = 1: wave w owns row w and every lane calls
+ *            dirty_mark_wave(wr = a[1] != 0, subject a[0]); subjects < MW * 64 * 2048
+ * ARITH      params sub, n (1..2^20), ...              one thread per case
+ *            DIV_GT  params gossip_t (>= 1)            in  x[n]                        out q[n], gt_mul
+ *            S16     s16_tick                          in  (entry, ref)[n]             out tick[n]
+ *            RG      rg_entry then rg_period           in  (slot, infp, P)[n]          out (period lo, hi, slot bits)[n]
+ *            KEY8                                      in  key[n]                      out shadow[n]
+ *            DELAY   params di (< 16), len (<= 256)    in  thr[len], x[n]              out ticks[n]
+ *            EPOCH   epoch_at                          in  ep_from[8], k[n]            out epoch[n] (0xFFFFFFFF: none)
+ *            PAYKEY  params MW, NS, ri, RXCAP, off     in  mask u64[MW], base_row[NS], shipped[popcount(mask)][2048],
+ *                    payload_key_at of payload             s[n] (each < NS <= MW * 64 * 2048)
+ *                    PAY_RX | ri, shipped chunks at    out key[n]
+ *                    byte offset off (a multiple of 4) of the receive buffer
+ * FEISTEL    params n (1..2^20), k0, k1, k2, k3        in  -
+ *            make_perm, feistel over [0, n)            out device[n], host[n] (the same functions compiled for the host)
+ * RING_MOVE  params N, B, B2 (powers of two, B <= B2)  in  rg[N][B], rhead[N], rtail[N] (rtail - rhead <= B)
+ *            launch_ring_move                          out rg2[N][B2] in/out */
+#define SWIM_PRIM_SCAN 0u
+#define SWIM_PRIM_SEG_SORT 1u
+#define SWIM_PRIM_ROUTING 2u
+#define SWIM_PRIM_WAVE 3u
+#define SWIM_PRIM_DIRTY 4u
+#define SWIM_PRIM_ARITH 5u
+#define SWIM_PRIM_FEISTEL 6u
+#define SWIM_PRIM_RING_MOVE 7u
+#define SWIM_PRIM_WAVE_APPEND 0u
+#define SWIM_PRIM_WAVE_RESERVE 1u
+#define SWIM_PRIM_WAVE_BLOCK_RESERVE 2u
+#define SWIM_PRIM_WAVE_SUM32 3u
+#define SWIM_PRIM_WAVE_MIN32 4u
+#define SWIM_PRIM_WAVE_SUM64 5u
+#define SWIM_PRIM_ARITH_DIV_GT 0u
+#define SWIM_PRIM_ARITH_S16 1u
+#define SWIM_PRIM_ARITH_RG 2u
+#define SWIM_PRIM_ARITH_KEY8 3u
+#define SWIM_PRIM_ARITH_DELAY 4u
+#define SWIM_PRIM_ARITH_EPOCH 5u
+#define SWIM_PRIM_ARITH_PAYKEY 6u
+int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t n_params, const void* in, size_t in_bytes,
+                         void* out, size_t out_bytes, uint32_t device);
+
 #ifdef __cplusplus
 }
 #endif

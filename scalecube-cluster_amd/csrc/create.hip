@@ -153,7 +153,7 @@ static int fill_dev(swim_handle* h) {
   // rounds kept for the infectedFrom replay (a delayed send arrives up to EMAX ticks after its round)
   while (d.LOGW < 4 * (maxSpread + 2) + 2 * ((d.EMAX + d.gossip_t - 1) / d.gossip_t + 1)) d.LOGW <<= 1;
   d.LOOKBACK = d.LOGW * d.gossip_t;
-  d.gt_mul = d.gossip_t == 1 ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / d.gossip_t);
+  d.gt_mul = gt_mul_of(d.gossip_t);
   // incarnation history of reborn (gossip, member) pairs (88 B per entry). 2^20 entries (92 MB) by default; a run
   // that asks for a large slot table (a storm: C4's heal rebirths a large share of the holder states) gets one
   // entry per 8 holder states, up to 2^24; SWIM_HIST_CAP overrides (a full table raises E_REBORN, info 1)

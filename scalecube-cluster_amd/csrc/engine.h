@@ -440,6 +440,12 @@ struct Dev {
   uint32_t* evp_n;               // [N]
 };
 
+// Dev::gt_mul for a gossip period of gossip_t >= 1 ticks: floor(2^32 / gossip_t), 2^32 - 1 for 1 (div_gt, dev_util.h).
+// swim_create and swim_debug_prim_eval both take it from here, so the division test pins the engine's own value
+static inline uint32_t gt_mul_of(uint32_t gossip_t) {
+  return gossip_t == 1 ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / gossip_t);
+}
+
 constexpr uint32_t ACKRES_ON = 1, ACKRES_DIRTY = 2;
 // one GPU with the dirty masks consulted and the 8-bit plane: the lister decides pinned live-row payloads from the
 // masks, and a speculative batch may queue no k_sync_diff on its untimed ticks (step.hip)

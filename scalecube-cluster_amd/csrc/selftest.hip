@@ -1,10 +1,13 @@
 // selftest.hip — swim_selftest_eval (include/swimhip_selftest.h): the device primitives the simulation kernels call,
-// evaluated on caller inputs in a gfx950 kernel, so the reference's known answers pin the device code itself.
+// evaluated on caller inputs in a gfx950 kernel, so the reference's known answers pin the device code itself; and
+// swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives the same way (engine only).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <vector>
 
 #include "../../include/swimhip.h"
+#include "../../include/swimhip_debug.h"
 #include "../../include/swimhip_selftest.h"
 #include "dev_util.h"
 
@@ -65,4 +68,372 @@ extern "C" int swim_selftest_eval(uint32_t op, const uint32_t* in, uint32_t* out
   if (din) hipFree(din);
   if (dout) hipFree(dout);
   return rc;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives on caller data. Every kernel
+// here only calls the engine's own functions (dev_util.h, engine.h, swim_common.h, route.hip, gossip.hip); the host
+// side checks every size and index first, so no input reaches a kernel that could index out of an allocation.
+namespace swim {
+
+__global__ void __launch_bounds__(256) k_seg_sort(uint64_t* key, uint32_t* val, uint64_t* tkey, uint32_t* tval,
+                                                  const uint32_t* off, const uint32_t* cnt, const uint32_t* sg,
+                                                  const uint32_t* nsg, uint32_t run, unsigned long long* fb);  // route.hip
+
+// a, r: [3][T] words per thread, T = gridDim.x * 256
+__global__ void __launch_bounds__(256) k_prim_wave(uint32_t sub, const uint32_t* a, uint32_t* r, uint32_t* ctr, uint32_t T) {
+  __shared__ uint32_t sh[5];
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t a0 = a[t], a1 = a[T + t], a2 = a[2 * T + t];
+  if (sub == SWIM_PRIM_WAVE_APPEND) {
+    if (a0) r[t] = wave_append(ctr);  // in a divergent branch, as k_scatter_rc calls it
+  } else if (sub == SWIM_PRIM_WAVE_RESERVE) {
+    r[t] = wave_reserve(ctr, a0);
+  } else if (sub == SWIM_PRIM_WAVE_BLOCK_RESERVE) {
+    r[t] = block_reserve(ctr, a0, sh);
+    r[T + t] = block_reserve(ctr, a1, sh);
+    r[2 * T + t] = block_reserve(ctr, a2, sh);
+  } else if (sub == SWIM_PRIM_WAVE_SUM32) {
+    r[t] = wave_sum(a0);
+  } else if (sub == SWIM_PRIM_WAVE_MIN32) {
+    r[t] = wave_min(a0);
+  } else {
+    const unsigned long long v = wave_sum(((unsigned long long)a1 << 32) | a0);
+    r[t] = (uint32_t)v;
+    r[T + t] = (uint32_t)(v >> 32);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_prim_dirty(uint32_t wave, const uint32_t* a, uint64_t* masks, uint32_t MW, uint32_t T) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (wave) {
+    dirty_mark_wave(masks + (size_t)(t >> 6) * MW, a[T + t] != 0, a[t]);
+  } else {
+    for (uint32_t j = 0; j < 3; ++j) {
+      const uint32_t s = a[j * T + t];
+      if (s != NEVER) dirty_mark(masks + (size_t)t * MW, s);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_prim_arith(const Dev d, uint32_t sub, const uint32_t* in, uint32_t* out, uint32_t n,
+                                                    uint32_t aux) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (sub == SWIM_PRIM_ARITH_DIV_GT) {
+    out[i] = div_gt(d, in[i]);
+  } else if (sub == SWIM_PRIM_ARITH_S16) {
+    out[i] = s16_tick((uint16_t)in[2ull * i], in[2ull * i + 1]);
+  } else if (sub == SWIM_PRIM_ARITH_RG) {
+    const uint32_t e = rg_entry(in[3ull * i], in[3ull * i + 1]);
+    const int64_t p = rg_period(e, in[3ull * i + 2]);
+    out[3ull * i] = (uint32_t)p;
+    out[3ull * i + 1] = (uint32_t)((uint64_t)p >> 32);
+    out[3ull * i + 2] = e & RG_SLOT;
+  } else if (sub == SWIM_PRIM_ARITH_KEY8) {
+    out[i] = key8(in[i]);
+  } else if (sub == SWIM_PRIM_ARITH_DELAY) {
+    out[i] = delay_ticks(d, aux, in[i]);
+  } else if (sub == SWIM_PRIM_ARITH_EPOCH) {
+    out[i] = (uint32_t)epoch_at(d, in[i]);
+  } else {
+    SyncMsg mm;
+    mm.payload = PAY_RX | aux;
+    mm.pin = NEVER;
+    out[i] = payload_key_at(d, mm, 0, in[i]);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_prim_feistel(uint32_t n, uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3,
+                                                      uint32_t* out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = feistel(make_perm(n, k0, k1, k2, k3), i);
+}
+
+namespace {
+
+// the call's device buffers: zero-filled, optionally loaded from host words, all freed when the call returns
+struct PrimBufs {
+  std::vector<void*> all;
+  int rc = SWIM_OK;
+  template <typename T>
+  T* get(size_t n, const void* src = nullptr, size_t n_src = 0) {
+    void* p = nullptr;
+    if (rc != SWIM_OK) return nullptr;
+    if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) {
+      rc = SWIM_ENOMEM;
+      return nullptr;
+    }
+    all.push_back(p);
+    if (hipMemset(p, 0, sizeof(T) * (n ? n : 1)) != hipSuccess ||
+        (src && n_src && hipMemcpy(p, src, sizeof(T) * n_src, hipMemcpyHostToDevice) != hipSuccess))
+      rc = SWIM_EDEVICE;
+    return (T*)p;
+  }
+  bool back(void* dst, const void* src, size_t bytes) {
+    if (rc == SWIM_OK && bytes && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = SWIM_EDEVICE;
+    return rc == SWIM_OK;
+  }
+  bool ran() {  // after the launches
+    if (rc == SWIM_OK && (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)) rc = SWIM_EDEVICE;
+    return rc == SWIM_OK;
+  }
+  ~PrimBufs() {
+    for (void* p : all) hipFree(p);
+  }
+};
+
+bool pow2(uint32_t x) { return x && !(x & (x - 1)); }
+constexpr uint64_t PRIM_MAX = 1ull << 22;  // elements of the largest array an op takes
+
+int prim_scan(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 1 || P[0] < 1 || P[0] > (1u << 20) || inb != 4ull * P[0] || outb != 4ull * (P[0] + 64)) return SWIM_EINVAL;
+  const uint32_t n = P[0];
+  PrimBufs b;
+  uint32_t* v = b.get<uint32_t>(n, in, n);
+  uint32_t* x = b.get<uint32_t>(n + 64, out, n + 64);
+  uint32_t* part = b.get<uint32_t>(1024);  // Dev::scan_part
+  if (b.rc == SWIM_OK) {
+    launch_scan(v, x, part, n, 0);
+    if (b.ran()) b.back(out, x, outb);
+  }
+  return b.rc;
+}
+
+int prim_seg_sort(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 5) return SWIM_EINVAL;
+  const uint64_t total = P[0], nmem = P[1], nlist = P[2];
+  const uint32_t run = P[3];
+  if (total < 1 || total > PRIM_MAX || nmem < 1 || nmem > (1u << 20) || nlist > (1u << 20) || !pow2(run) || run < 2 ||
+      run > SORT_MAX || inb != 12 * total + 8 * nmem + 4 * nlist || outb != 8 + 12 * total)
+    return SWIM_EINVAL;
+  const uint32_t *val = in + 2 * total, *off = val + total, *cnt = off + nmem, *sg = cnt + nmem;
+  for (uint64_t i = 0; i < nmem; ++i)
+    if ((uint64_t)off[i] + cnt[i] > total) return SWIM_EINVAL;
+  for (uint64_t i = 0; i < nlist; ++i)
+    if (sg[i] >= nmem) return SWIM_EINVAL;
+  const uint32_t nl = (uint32_t)nlist;
+  PrimBufs b;
+  uint64_t* dk = b.get<uint64_t>(total, in, total);
+  uint32_t* dv = b.get<uint32_t>(total, val, total);
+  uint64_t* tk = b.get<uint64_t>(total);
+  uint32_t* tv = b.get<uint32_t>(total);
+  uint32_t* doff = b.get<uint32_t>(nmem, off, nmem);
+  uint32_t* dcnt = b.get<uint32_t>(nmem, cnt, nmem);
+  uint32_t* dsg = b.get<uint32_t>(nlist, sg, nlist);
+  uint32_t* dn = b.get<uint32_t>(1, &nl, 1);
+  unsigned long long* fb = b.get<unsigned long long>(FB_N);
+  if (b.rc == SWIM_OK) {
+    hipLaunchKernelGGL(k_seg_sort, dim3(1024), dim3(256), 0, 0, dk, dv, tk, tv, doff, dcnt, dsg, dn, run,
+                       P[4] ? fb : nullptr);
+    if (b.ran() && b.back(out, fb + FB_SORT_MERGE, 8) && b.back(out + 2, dk, 8 * total)) b.back(out + 2 + 2 * total, dv, 4 * total);
+  }
+  return b.rc;
+}
+
+int prim_routing(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 6) return SWIM_EINVAL;
+  const uint64_t N = P[0], RCAP = P[1], SLOTS = P[3], nraw = P[2] < RCAP ? P[2] : RCAP;
+  if (N < 1 || N > (1u << 20) || RCAP < 1 || RCAP > PRIM_MAX || SLOTS < 1 || SLOTS > PRIM_MAX || !pow2(P[4]) || P[4] < 2 ||
+      P[4] > SORT_MAX || inb != 8 * nraw + 8 * SLOTS || outb != 8 * RCAP + 8 + 4 * RCAP + 12 * N + 8)
+    return SWIM_EINVAL;
+  const uint64_t* raw = (const uint64_t*)in;
+  for (uint64_t i = 0; i < nraw; ++i)
+    if ((raw[i] >> 32) >= N || (uint32_t)raw[i] >= SLOTS) return SWIM_EINVAL;
+  uint32_t *o_slot = out + 2 * RCAP + 2, *o_off = o_slot + RCAP, *o_cnt = o_off + N, *o_sg = o_cnt + N, *o_nsg = o_sg + N;
+  PrimBufs b;
+  Dev d;  // only the fields the routing kernels read (route.hip)
+  memset(&d, 0, sizeof d);
+  d.N = (uint32_t)N;
+  d.RCAP = (uint32_t)RCAP;
+  d.sort_cap = P[4];
+  d.rc_raw = b.get<uint64_t>(RCAP, raw, nraw);
+  d.rc_n = b.get<uint32_t>(1, &P[2], 1);
+  d.slot_gid = b.get<uint64_t>(SLOTS, raw + nraw, SLOTS);
+  d.rc_cnt = b.get<uint32_t>(N);
+  d.rc_fill = b.get<uint32_t>(N);
+  d.rc_off = b.get<uint32_t>(N, o_off, N);
+  d.scan_part = b.get<uint32_t>(1024);
+  d.rc_key = b.get<uint64_t>(RCAP, out, RCAP);
+  d.rc_slot = b.get<uint32_t>(RCAP, o_slot, RCAP);
+  d.rc_key2 = b.get<uint64_t>(RCAP);
+  d.rc_slot2 = b.get<uint32_t>(RCAP);
+  d.sg_list = b.get<uint32_t>(N, o_sg, N);
+  d.nsg = b.get<uint32_t>(1);
+  unsigned long long* fb = b.get<unsigned long long>(FB_N);
+  d.fb = P[5] ? fb : nullptr;
+  if (b.rc == SWIM_OK) {
+    launch_receipt_routing(d, 0);
+    o_nsg[1] = 0;
+    if (b.ran() && b.back(out, d.rc_key, 8 * RCAP) && b.back(out + 2 * RCAP, fb + FB_SORT_MERGE, 8) &&
+        b.back(o_slot, d.rc_slot, 4 * RCAP) && b.back(o_off, d.rc_off, 4 * N) && b.back(o_cnt, d.rc_cnt, 4 * N) &&
+        b.back(o_sg, d.sg_list, 4 * N))
+      b.back(o_nsg, d.nsg, 4);
+  }
+  return b.rc;
+}
+
+int prim_wave(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 2 || P[0] > SWIM_PRIM_WAVE_SUM64 || P[1] < 1 || P[1] > 64) return SWIM_EINVAL;
+  const uint32_t T = P[1] * 256;
+  if (inb != 12ull * T || outb != 12ull * T + 16) return SWIM_EINVAL;
+  PrimBufs b;
+  uint32_t* a = b.get<uint32_t>(3 * T, in, 3 * T);
+  uint32_t* r = b.get<uint32_t>(3 * T + 4, out, 3 * T + 4);
+  if (b.rc == SWIM_OK) {
+    hipLaunchKernelGGL(k_prim_wave, dim3(P[1]), dim3(256), 0, 0, P[0], a, r, r + 3 * T, T);
+    if (b.ran()) b.back(out, r, outb);
+  }
+  return b.rc;
+}
+
+int prim_dirty(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 3 || P[0] > 1 || P[1] < 1 || P[1] > 64 || P[2] < 1 || P[2] > MSW) return SWIM_EINVAL;
+  const uint32_t T = P[1] * 256, MW = P[2], rows = P[0] ? T / 64 : T, lim = MW * 64 * CH;
+  if (inb != 12ull * T || outb != 8ull * rows * MW) return SWIM_EINVAL;
+  for (uint32_t i = 0; i < (P[0] ? T : 3 * T); ++i)  // wave = 1: every lane's subject, written or not
+    if (in[i] >= lim && (P[0] || in[i] != NEVER)) return SWIM_EINVAL;
+  PrimBufs b;
+  uint32_t* a = b.get<uint32_t>(3 * T, in, 3 * T);
+  uint64_t* m = b.get<uint64_t>((size_t)rows * MW, out, (size_t)rows * MW);
+  if (b.rc == SWIM_OK) {
+    hipLaunchKernelGGL(k_prim_dirty, dim3(P[1]), dim3(256), 0, 0, P[0], a, m, MW, T);
+    if (b.ran()) b.back(out, m, outb);
+  }
+  return b.rc;
+}
+
+int prim_arith(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np < 2 || P[0] > SWIM_PRIM_ARITH_PAYKEY || P[1] < 1 || P[1] > (1u << 20)) return SWIM_EINVAL;
+  const uint32_t sub = P[0], n = P[1];
+  static const size_t NP[] = {3, 2, 2, 2, 4, 2, 7};
+  if (np != NP[sub]) return SWIM_EINVAL;
+  PrimBufs b;
+  Dev d;  // only the fields the helper under test reads (dev_util.h)
+  memset(&d, 0, sizeof d);
+  uint64_t win = n, wout = n;  // words of in that are per-case inputs (they follow the op's tables), words of out
+  uint32_t aux = 0;
+  const uint32_t* cases = in;
+  if (sub == SWIM_PRIM_ARITH_DIV_GT) {
+    if (P[2] < 1) return SWIM_EINVAL;
+    d.gossip_t = P[2];
+    d.gt_mul = gt_mul_of(P[2]);
+    wout = (uint64_t)n + 1;
+  } else if (sub == SWIM_PRIM_ARITH_S16) {
+    win = 2ull * n;
+  } else if (sub == SWIM_PRIM_ARITH_RG) {
+    win = wout = 3ull * n;
+  }
+  if (sub <= SWIM_PRIM_ARITH_KEY8 && inb != 4 * win) return SWIM_EINVAL;
+  if (sub == SWIM_PRIM_ARITH_DELAY) {
+    const uint32_t di = P[2], len = P[3];
+    if (di >= DTAB || len > 256 || inb != 4ull * (len + n)) return SWIM_EINVAL;
+    std::vector<uint32_t> thr(DTAB * 256, 0), ln(DTAB, 0);
+    memcpy(thr.data() + di * 256, in, 4ull * len);
+    ln[di] = len;
+    d.dly_thr = b.get<uint32_t>(DTAB * 256, thr.data(), DTAB * 256);
+    d.dly_len = b.get<uint32_t>(DTAB, ln.data(), DTAB);
+    aux = di;
+    cases = in + len;
+  } else if (sub == SWIM_PRIM_ARITH_EPOCH) {
+    if (inb != 4ull * (MAX_EPOCHS + n)) return SWIM_EINVAL;
+    memcpy(d.ep_from, in, 4 * MAX_EPOCHS);
+    cases = in + MAX_EPOCHS;
+  } else if (sub == SWIM_PRIM_ARITH_PAYKEY) {
+    const uint32_t MW = P[2], NS = P[3], ri = P[4], RXCAP = P[5], off = P[6];
+    if (MW < 1 || MW > MSW || NS < 1 || NS > MW * 64 * CH || ri >= RXCAP || RXCAP > 1024 || (off & 3u) || off > (1u << 20) ||
+        inb < 8ull * MW)
+      return SWIM_EINVAL;
+    const uint64_t* mask = (const uint64_t*)in;
+    uint64_t nship = 0;
+    for (uint32_t q = 0; q < MW; ++q) nship += (uint64_t)__builtin_popcountll(mask[q]);
+    if (inb != 4 * (2ull * MW + NS + nship * CH + n)) return SWIM_EINVAL;
+    const uint32_t *base = in + 2 * MW, *ship = base + NS;
+    cases = ship + nship * CH;
+    for (uint32_t i = 0; i < n; ++i)
+      if (cases[i] >= NS) return SWIM_EINVAL;
+    std::vector<uint64_t> rm((size_t)RXCAP * MW, 0), ro(RXCAP, 0);
+    memcpy(rm.data() + (size_t)ri * MW, mask, 8ull * MW);
+    ro[ri] = off;
+    d.MW = MW;
+    d.rx_mask = b.get<uint64_t>(rm.size(), rm.data(), rm.size());
+    d.rx_off = b.get<uint64_t>(RXCAP, ro.data(), RXCAP);
+    d.base_row = b.get<uint32_t>(NS, base, NS);
+    d.xa_recv = b.get<uint8_t>(off + 4 * nship * CH);
+    if (b.rc == SWIM_OK && nship && hipMemcpy(d.xa_recv + off, ship, 4 * nship * CH, hipMemcpyHostToDevice) != hipSuccess)
+      b.rc = SWIM_EDEVICE;
+    aux = ri;
+  }
+  if (outb != 4 * wout) return SWIM_EINVAL;
+  uint32_t* din = b.get<uint32_t>(win, cases, win);
+  uint32_t* dout = b.get<uint32_t>(wout);
+  if (b.rc == SWIM_OK) {
+    hipLaunchKernelGGL(k_prim_arith, dim3(cdiv(n, 256)), dim3(256), 0, 0, d, sub, din, dout, n, aux);
+    if (b.ran() && b.back(out, dout, 4ull * n * (sub == SWIM_PRIM_ARITH_RG ? 3 : 1)) && sub == SWIM_PRIM_ARITH_DIV_GT)
+      out[n] = d.gt_mul;
+  }
+  return b.rc;
+}
+
+int prim_feistel(const uint32_t* P, size_t np, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 5 || P[0] < 1 || P[0] > (1u << 20) || inb != 0 || outb != 8ull * P[0]) return SWIM_EINVAL;
+  const uint32_t n = P[0];
+  PrimBufs b;
+  uint32_t* o = b.get<uint32_t>(n);
+  if (b.rc == SWIM_OK) {
+    hipLaunchKernelGGL(k_prim_feistel, dim3(cdiv(n, 256)), dim3(256), 0, 0, n, P[1], P[2], P[3], P[4], o);
+    if (b.ran() && b.back(out, o, 4ull * n)) {
+      const FeistelPerm p = make_perm(n, P[1], P[2], P[3], P[4]);
+      for (uint32_t i = 0; i < n; ++i) out[n + i] = feistel(p, i);
+    }
+  }
+  return b.rc;
+}
+
+int prim_ring_move(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 3) return SWIM_EINVAL;
+  const uint64_t N = P[0], B = P[1], B2 = P[2];
+  if (N < 1 || N > (1u << 16) || !pow2(P[1]) || !pow2(P[2]) || B > B2 || N * B2 > PRIM_MAX || inb != 4 * (N * B + 2 * N) ||
+      outb != 4 * N * B2)
+    return SWIM_EINVAL;
+  const uint32_t *rh = in + N * B, *rt = rh + N;
+  for (uint64_t m = 0; m < N; ++m)
+    if (rt[m] - rh[m] > B) return SWIM_EINVAL;  // positions are absolute and wrap
+  PrimBufs b;
+  uint32_t* rg = b.get<uint32_t>(N * B, in, N * B);
+  uint32_t* rg2 = b.get<uint32_t>(N * B2, out, N * B2);
+  uint32_t* dh = b.get<uint32_t>(N, rh, N);
+  uint32_t* dt = b.get<uint32_t>(N, rt, N);
+  if (b.rc == SWIM_OK) {
+    launch_ring_move(rg, rg2, dh, dt, (uint32_t)N, (uint32_t)B, (uint32_t)B2, nullptr);
+    if (b.ran()) b.back(out, rg2, outb);
+  }
+  return b.rc;
+}
+
+}  // namespace
+}  // namespace swim
+
+extern "C" int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t n_params, const void* in, size_t in_bytes,
+                                    void* out, size_t out_bytes, uint32_t device) {
+  using namespace swim;
+  if (op > SWIM_PRIM_RING_MOVE || !params || n_params > 8 || !out || (in_bytes && !in) || ((uintptr_t)in & 7u) ||
+      ((uintptr_t)out & 7u))
+    return SWIM_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= (int)device || hipSetDevice((int)device) != hipSuccess)
+    return SWIM_EDEVICE;
+  const uint32_t* i32 = (const uint32_t*)in;
+  uint32_t* o32 = (uint32_t*)out;
+  switch (op) {
+    case SWIM_PRIM_SCAN: return prim_scan(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_SEG_SORT: return prim_seg_sort(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_ROUTING: return prim_routing(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_WAVE: return prim_wave(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_DIRTY: return prim_dirty(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_ARITH: return prim_arith(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_FEISTEL: return prim_feistel(params, n_params, in_bytes, o32, out_bytes);
+    default: return prim_ring_move(params, n_params, i32, in_bytes, o32, out_bytes);
+  }
 }

@@ -247,7 +247,32 @@ DEBUG_SIGNATURES = {
     "swim_debug_set_incarnation": (C.c_int, [_H, C.c_uint32, C.c_uint32]),
     "swim_debug_diff_dirty": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
     "swim_debug_dirty_check": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
+    "swim_debug_prim_eval": (C.c_int, [C.c_uint32, _U32P, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_uint32]),
 }
+# swim_debug_prim_eval: ops, and the sub-ops of PRIM_WAVE and PRIM_ARITH (include/swimhip_debug.h has the layouts)
+(PRIM_SCAN, PRIM_SEG_SORT, PRIM_ROUTING, PRIM_WAVE, PRIM_DIRTY, PRIM_ARITH, PRIM_FEISTEL, PRIM_RING_MOVE) = range(8)
+(WAVE_APPEND, WAVE_RESERVE, WAVE_BLOCK_RESERVE, WAVE_SUM32, WAVE_MIN32, WAVE_SUM64) = range(6)
+(ARITH_DIV_GT, ARITH_S16, ARITH_RG, ARITH_KEY8, ARITH_DELAY, ARITH_EPOCH, ARITH_PAYKEY) = range(7)
+
+
+def prim_eval_rc(lib, op, params, inp, out, device=0):
+    """swim_debug_prim_eval on numpy arrays: `inp` (C-contiguous, 8-byte aligned; None: no input) is read and `out`
+    is read and written in place; returns the code (SWIM_EINVAL for anything the op's layout does not allow)."""
+    fn = lib.swim_debug_prim_eval
+    fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_prim_eval"]
+    p = (C.c_uint32 * max(1, len(params)))(*[int(x) & 0xFFFFFFFF for x in params])
+    assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and (inp is None or inp.flags["C_CONTIGUOUS"])
+    return fn(op, p, len(params), inp.ctypes.data if inp is not None and inp.nbytes else None,
+              inp.nbytes if inp is not None else 0, out.ctypes.data, out.nbytes, device)
+
+
+def prim_eval(lib, op, params, inp, out, device=0):
+    """The same, raising on any code but SWIM_OK; returns `out`."""
+    rc = prim_eval_rc(lib, op, params, inp, out, device)
+    if rc != 0:
+        raise RuntimeError(f"swim_debug_prim_eval(op={op}, params={list(params)}) rc={rc}")
+    return out
 DD_NAMES = ["skipped", "streamed", "msg_skipped", "rebases", "dirty_rows", "pin_decided", "diff_elided", "diff_halts"]
 CAP_NAMES = ["slots", "ring", "receipts", "replay", "history", "growths"]
 
