@@ -141,7 +141,39 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
  * FEISTEL    params n (1..2^20), k0, k1, k2, k3        in  -
  *            make_perm, feistel over [0, n)            out device[n], host[n] (the same functions compiled for the host)
  * RING_MOVE  params N, B, B2 (powers of two, B <= B2)  in  rg[N][B], rhead[N], rtail[N] (rtail - rhead <= B)
- *            launch_ring_move                          out rg2[N][B2] in/out */
+ *            launch_ring_move                          out rg2[N][B2] in/out
+ *
+ * SYNC_DIFF  k_sync_diff and its lister k_ack_resolve (sync_diff.hip) on a Dev that holds only what the two kernels read,
+ *            queued through launch_diff_listed (the diff alone) or launch_diff (the lister, then the diff) as a step
+ *            queues them, on the messages of one buffer (that of tick k - 1). The sizes follow from N by the expressions
+ *            swim_create uses: NS = N rounded up to 8, NS8 to 16, NCHUNK = NS / 2048 and NMETA = NS / 1024 rounded up,
+ *            MW = NCHUNK / 64 rounded up, nit = NCHUNK / 4 rounded up (narrow items per payload).
+ *            params (15): N subjects (1 .. 3 * 64 * 2048); R rows (1..64: members lo .. lo + R - 1); flags (SWIM_PRIM_SD_*);
+ *              nmsg; MSGCAP (nmsg <= MSGCAP <= 4096); ARENA_ROWS A (<= 64); POOLCAP (<= 2^22); k (>= 1: the tick, buffer
+ *              (k - 1) & 1); grid (k_sync_diff's blocks, <= 4096; 0: the engine's own); sentinel; nnar, nwide (the lists'
+ *              lengths, with SD_LISTS); lo, nrx (received payloads <= 64; with SD_SHARDED); ls (launch_diff's: 1 = LS_SPEC,
+ *              2 = LS_NODIFF; with SD_LISTER)
+ *            flags: SD_K8 the rows have the 8-bit plane (derived here with key8; narrow entries need it);
+ *              SD_LISTS (mode A) ackres is on and k_sync_diff streams the caller's two lists, else every message wide;
+ *              SD_SHARDED (mode A) W = 2: k_sync_diff<true>, a narrow entry per message, payloads PAY_RX | ri;
+ *              SD_LISTER (mode B, one GPU) launch_diff(k, ls): k_ack_resolve builds the lists; SD_DIRTY with it: the
+ *              lister consults the rows' dirty masks (with SD_K8 too: diff_elidable, the inbound lists are walked)
+ *            in  dirty u64[R][3] (MS::dirty); SD_SHARDED: rx_mask u64[nrx][MW], rx_off u64[nrx] (byte offsets into the
+ *                receive buffer, multiples of 16); rowk[R][NS]; arena[A][NS]; msgs[nmsg][6] = src, dst, kind, payload,
+ *                pin, tln (ncand = 0); SD_LISTS: narrow[nnar][4], wide[nwide][4] (message, sender, receiver, place:
+ *                desc_pay; one GPU narrow: item << 4 | chunk bits); SD_LISTER: tl_tick[2][R], tl_n[2][R], tlog[2][R][16],
+ *                m_head[R], m_next[nmsg]; SD_SHARDED: base_row[NS], receive buffer [chunks][2048]
+ *            out pool u64[POOLCAP + 64] (every word preset to sentinel | sentinel << 32; the last 64 are guard words);
+ *                u64[12] = C_DIFFMSG, C_DIFFMSG_ALL, C_DIFFWIDE, C_DIFFWIDE_ALL, C_ACKRES, C_ACKRES_ALL, C_DSTREAM,
+ *                C_DSUBJ, C_DSUBJ_ALL, C_DMSGSKIP, pin-decided, 0; cstat u64[NCHUNK][3] (0 when SD_SHARDED);
+ *                chunk_meta[nmsg][NMETA][2] (preset to sentinel); (kind, ncand, pin)[nmsg]; arena[A][NS];
+ *                narrow list [ncap][4] (ncap = MSGCAP * nit, SD_SHARDED: MSGCAP) and wide list [MSGCAP][4] (preset to
+ *                sentinel); pool_used, err, narrow length, wide length, halt[3], hflag[HF_STREAMED]
+ *            EINVAL before any launch: a src / dst outside the rows (a PAY_RX payload's src: outside N), a payload or pin
+ *            that is no arena row (or PAY_RX | ri with ri >= nrx), a list entry whose message, rows, place, item or chunk
+ *            bits do not exist, a log subject >= N, an m_head / m_next link >= nmsg or a list that does not end, chunk-mask
+ *            bits past NCHUNK, an rx_off that is no multiple of 16 or whose popcount(mask) chunks pass the receive buffer,
+ *            non-zero padding keys between N and NS, k = 0, flags that do not go together */
 #define SWIM_PRIM_SCAN 0u
 #define SWIM_PRIM_SEG_SORT 1u
 #define SWIM_PRIM_ROUTING 2u
@@ -150,6 +182,12 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
 #define SWIM_PRIM_ARITH 5u
 #define SWIM_PRIM_FEISTEL 6u
 #define SWIM_PRIM_RING_MOVE 7u
+#define SWIM_PRIM_SYNC_DIFF 8u
+#define SWIM_PRIM_SD_K8 1u
+#define SWIM_PRIM_SD_LISTER 2u
+#define SWIM_PRIM_SD_LISTS 4u
+#define SWIM_PRIM_SD_SHARDED 8u
+#define SWIM_PRIM_SD_DIRTY 16u
 #define SWIM_PRIM_WAVE_APPEND 0u
 #define SWIM_PRIM_WAVE_RESERVE 1u
 #define SWIM_PRIM_WAVE_BLOCK_RESERVE 2u

@@ -74,7 +74,8 @@ static int fill_dev(swim_handle* h) {
   Dev& d = h->d;
   std::memset(&d, 0, sizeof(d));
   d.N = c.n_members;
-  d.NS = (c.n_members + 7u) & ~7u;
+  const KeyPlaneSizes kp = key_plane_sizes(c.n_members);
+  d.NS = kp.NS;
   d.W = h->spec.world ? h->spec.world : 1u;
   d.rank = h->spec.rank;
   d.XW = 1;
@@ -222,8 +223,8 @@ static int fill_dev(swim_handle* h) {
   uint64_t mc = N / d.sync_t * 4 + N / d.ping_t + 1024;
   if (c.init_mode == SWIM_INIT_COLD_JOIN) mc = std::max<uint64_t>(mc, N + 1024);
   d.MSGCAP = (uint32_t)mc;
-  d.NCHUNK = (uint32_t)((d.NS + CH - 1) / CH);
-  d.NMETA = (uint32_t)((d.NS + MCH - 1) / MCH);
+  d.NCHUNK = kp.NCHUNK;
+  d.NMETA = kp.NMETA;
   d.POOLCAP = (uint32_t)std::min<uint64_t>(1ull << 26, std::max<uint64_t>(1ull << 20, N * 64));
   d.EVCAP = c.event_cap ? c.event_cap : (1u << 20);
   // first receipts per tick: routed to P4 (RCAP), shipped to the other row shards (DCAP)
@@ -252,7 +253,7 @@ static int fill_dev(swim_handle* h) {
     d.ARENA_ROWS = 1;
     d.POOLCAP = 1024;
   }
-  d.NS8 = (c.n_members + 15u) & ~15u;  // row stride of the 8-bit shadow plane
+  d.NS8 = kp.NS8;  // row stride of the 8-bit shadow plane
   // the per-tick contact rows follow the row width; SWIM_CAPS rx=...: contact pairs past it replay their whole window
   d.CRCAP = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(4096, (512ull << 20) / (8ull * d.QW)));
   if (rx_cap != NEVER) d.CRCAP = rx_cap;
@@ -268,12 +269,12 @@ static int fill_dev(swim_handle* h) {
   // SWIM_NO_DIRTY keeps the masks but never consults them (measurements, and the tests' reference path)
   // (RUMOR mode sends no SYNC: no masks)
   // the masks and the rebase counters live in the members' records' spare words (MS), no allocation of their own
-  if (d.W == 1 && !d.implicit && d.mode != SWIM_MODE_RUMOR && (d.NCHUNK + 63) / 64 <= MSW) {
-    d.MW = (d.NCHUNK + 63) / 64;
+  if (d.W == 1 && !d.implicit && d.mode != SWIM_MODE_RUMOR && kp.MW <= MSW) {
+    d.MW = kp.MW;
     if (d.ackres && !getenv("SWIM_NO_DIRTY")) d.ackres |= ACKRES_DIRTY;
   }
   if (d.W > 1) {
-    d.MW = (d.NCHUNK + 63) / 64;
+    d.MW = kp.MW;
     d.NSCAP = 1u << 16;
     d.RRCAP = d.NL;
     d.RQCAP = d.MSGCAP;

@@ -164,7 +164,8 @@ struct alignas(16) MS {
   uint64_t dirty[3];
   unsigned long long cstat[3];
 };
-constexpr uint32_t MSW = 3;  // mask words a member record holds: 196 608 members, more than a stored table can have
+constexpr uint32_t MSW = 3;  // mask words a member record holds: 393 216 members (MSW * 64 chunks of CH subjects), more
+                             // than a stored table can have
 static_assert(sizeof(MS) == 128, "one cache line per member");
 
 struct Dev {
@@ -446,6 +447,23 @@ static inline uint32_t gt_mul_of(uint32_t gossip_t) {
   return gossip_t == 1 ? 0xFFFFFFFFu : (uint32_t)((1ull << 32) / gossip_t);
 }
 
+// the sizes of the key plane and of the SYNC diff's work that follow from the member count alone: the row strides (N
+// rounded up to 8 keys and to 16 shadow bytes: 32-B and 16-B aligned rows), the 2048-subject chunks, the 1024-subject
+// candidate segments and the u64 words of a chunk mask (whether masks are kept is the caller's decision: Dev::MW may
+// be 0). swim_create and swim_debug_prim_eval both take them from here, so the diff tests run on the engine's sizes
+struct KeyPlaneSizes {
+  uint32_t NS, NS8, NCHUNK, NMETA, MW;
+};
+static inline KeyPlaneSizes key_plane_sizes(uint32_t N) {
+  KeyPlaneSizes z;
+  z.NS = (N + 7u) & ~7u;
+  z.NS8 = (N + 15u) & ~15u;
+  z.NCHUNK = (uint32_t)((z.NS + CH - 1) / CH);
+  z.NMETA = (uint32_t)((z.NS + MCH - 1) / MCH);
+  z.MW = (z.NCHUNK + 63) / 64;
+  return z;
+}
+
 constexpr uint32_t ACKRES_ON = 1, ACKRES_DIRTY = 2;
 // one GPU with the dirty masks consulted and the 8-bit plane: the lister decides pinned live-row payloads from the
 // masks, and a speculative batch may queue no k_sync_diff on its untimed ticks (step.hip)
@@ -504,8 +522,10 @@ void launch_init(const Dev& d, void* stream);
 // launch_diff's ls: LS_SPEC, | LS_NODIFF (one GPU with dirty masks and the 8-bit plane; else ignored): only the lister
 // is queued, told that no k_sync_diff follows it; launch_diff_listed is that diff alone, for the host after a diff-halt
 // (not speculative)
-void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, uint32_t ls = 0u);
-void launch_diff_listed(const Dev& d, uint32_t k, void* stream);
+// grid: k_sync_diff's blocks (0: the engine's own, DIFF_WAVES per CU; the known-answer tests set small ones)
+void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, uint32_t ls = 0u,
+                 uint32_t grid = 0u);
+void launch_diff_listed(const Dev& d, uint32_t k, void* stream, uint32_t grid = 0u);
 // split: the previous tick ran the gossip plane (routed receipts for P4: k_member_tick parks the members with many,
 // k_inbox_apply runs their P4, a second k_member_tick launch their P5 and P6)
 void launch_member(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, bool spec = false,

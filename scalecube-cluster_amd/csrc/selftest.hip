@@ -1,8 +1,10 @@
 // selftest.hip — swim_selftest_eval (include/swimhip_selftest.h): the device primitives the simulation kernels call,
 // evaluated on caller inputs in a gfx950 kernel, so the reference's known answers pin the device code itself; and
-// swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives the same way (engine only).
+// swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives and the SYNC diff with its
+// lister the same way (engine only).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -412,13 +414,242 @@ int prim_ring_move(const uint32_t* P, size_t np, const uint32_t* in, size_t inb,
   return b.rc;
 }
 
+// k_sync_diff and k_ack_resolve on a Dev that holds only what the two kernels read (sync_diff.hip), launched through
+// launch_diff / launch_diff_listed as step.hip launches them. Layout: include/swimhip_debug.h.
+int prim_sync_diff(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 15) return SWIM_EINVAL;
+  const uint32_t N = P[0], R = P[1], fl = P[2], nmsg = P[3], MSGCAP = P[4], AR = P[5], POOLCAP = P[6], k = P[7], grid = P[8],
+                 sent = P[9], nnar = P[10], nwide = P[11], lo = P[12], nrx = P[13], ls = P[14];
+  const bool k8 = fl & SWIM_PRIM_SD_K8, lister = fl & SWIM_PRIM_SD_LISTER, lists = fl & SWIM_PRIM_SD_LISTS,
+             sharded = fl & SWIM_PRIM_SD_SHARDED, dirty = fl & SWIM_PRIM_SD_DIRTY;
+  if (N < 1 || N > MSW * 64 * CH || R < 1 || R > 64 || fl > 31 || MSGCAP < 1 || MSGCAP > 4096 || nmsg > MSGCAP || AR > 64 ||
+      POOLCAP > (1u << 22) || k < 1 || k >= (1u << 31) || grid > 4096 || ls > (LS_SPEC | LS_NODIFF) || nrx > 64 ||
+      (uint64_t)lo + R > N)
+    return SWIM_EINVAL;
+  if ((lister && (lists || sharded)) || (!lister && (dirty || ls)) || (!lists && (nnar || nwide)) ||
+      (!sharded && (lo || nrx)) || (nnar && !k8))
+    return SWIM_EINVAL;
+  const KeyPlaneSizes z = key_plane_sizes(N);
+  const uint32_t NS = z.NS, NS8 = z.NS8, NCHUNK = z.NCHUNK, NMETA = z.NMETA, MW = z.MW;
+  const uint32_t nit = (NCHUNK + NPER - 1) / NPER, b = (k - 1) & 1u;
+  const uint64_t ncap = sharded ? MSGCAP : (uint64_t)MSGCAP * nit;  // narrow entries: per message, or per item
+  if (nnar > ncap || nwide > MSGCAP) return SWIM_EINVAL;
+
+  // ---- the input's parts ----
+  const uint64_t w_dirty = 2ull * MSW * R, w_rx = sharded ? 2ull * MW * nrx + 2ull * nrx : 0, w_rows = (uint64_t)R * NS,
+                 w_arena = (uint64_t)AR * NS, w_msgs = 6ull * nmsg, w_lists = 4ull * nnar + 4ull * nwide,
+                 w_log = lister ? 4ull * R + 2ull * R * TL + R + nmsg : 0, w_base = sharded ? NS : 0;
+  const uint64_t fixed = w_dirty + w_rx + w_rows + w_arena + w_msgs + w_lists + w_log + w_base;
+  if ((inb & 3u) || inb / 4 < fixed || (inb / 4 - fixed) % CH || (!sharded && inb / 4 != fixed)) return SWIM_EINVAL;
+  const uint64_t nship = (inb / 4 - fixed) / CH;  // shipped chunks in the receive buffer
+  if (nship > 1024) return SWIM_EINVAL;
+  const uint64_t w_out = 2ull * (POOLCAP + 64) + 24 + 6ull * NCHUNK + 2ull * NMETA * nmsg + 3ull * nmsg + w_arena + 4 * ncap +
+                         4ull * MSGCAP + 8;
+  if (outb != 4 * w_out) return SWIM_EINVAL;
+  const uint64_t* i_dirty = (const uint64_t*)in;
+  const uint64_t *i_rxm = i_dirty + (size_t)MSW * R, *i_rxo = i_rxm + (sharded ? (size_t)MW * nrx : 0);
+  const uint32_t* i_rows = in + w_dirty + w_rx;
+  const uint32_t *i_arena = i_rows + w_rows, *i_msgs = i_arena + w_arena, *i_nar = i_msgs + w_msgs, *i_wide = i_nar + 4ull * nnar;
+  const uint32_t *i_tick = i_wide + 4ull * nwide, *i_tln = i_tick + 2ull * R, *i_tlog = i_tln + 2ull * R,
+                 *i_head = i_tlog + 2ull * R * TL, *i_next = i_head + R;
+  const uint32_t *i_base = in + (fixed - w_base), *i_ship = in + fixed;
+
+  // ---- host checks: nothing below may let a kernel index outside an allocation ----
+  for (uint32_t r = 0; r < R + AR + (sharded ? 1u : 0u); ++r) {  // padding keys are 0 (absent)
+    const uint32_t* row = r < R ? i_rows + (size_t)r * NS : r < R + AR ? i_arena + (size_t)(r - R) * NS : i_base;
+    for (uint32_t s = N; s < NS; ++s)
+      if (row[s]) return SWIM_EINVAL;
+  }
+  const auto row_of = [&](uint32_t m) { return m >= lo && m - lo < R; };
+  const auto pay_ok = [&](uint32_t pay) {  // a message's payload, or a list entry's place without its flag values
+    if (pay & PAY_RX) return sharded && !(pay & DESC_PIN) && (pay & ~PAY_RX) < nrx;
+    return pay < AR;
+  };
+  for (uint32_t i = 0; i < nmsg; ++i) {
+    const uint32_t *m = i_msgs + 6ull * i, src = m[0], dst = m[1], pay = m[3], pin = m[4];
+    const bool rx = pay != NEVER && (pay & PAY_RX);
+    if (!(rx ? src < N : row_of(src)) || !row_of(dst) || (pay != NEVER && !pay_ok(pay)) || (pin != NEVER && pin >= AR))
+      return SWIM_EINVAL;
+  }
+  for (uint32_t i = 0; i < nnar + nwide; ++i) {
+    const uint32_t *e = i_nar + 4ull * i, w = e[3];
+    const bool nar = i < nnar, rx = sharded && w != NEVER && w != DESC_DEFER && !(w & DESC_PIN) && (w & PAY_RX);
+    if (e[0] >= nmsg || !(rx ? e[1] < N : row_of(e[1])) || !row_of(e[2])) return SWIM_EINVAL;
+    if (nar && !sharded) {  // item index << 4 | the item's chunks to stream
+      const uint32_t t = w >> 4, m4 = w & 15u;
+      if (t >= nit || (m4 >> (NCHUNK - NPER * t < NPER ? NCHUNK - NPER * t : NPER))) return SWIM_EINVAL;
+    } else if (nar) {  // a local sender's live row, or a peer's payload
+      if (w != NEVER && !rx) return SWIM_EINVAL;
+      if (rx && !pay_ok(w)) return SWIM_EINVAL;
+    } else if (w != NEVER && w != DESC_DEFER) {
+      if (w & DESC_PIN ? (w & ~DESC_PIN) >= AR : !pay_ok(w)) return SWIM_EINVAL;
+    }
+  }
+  if (lister) {
+    for (uint64_t i = 0; i < 2ull * R * TL; ++i)
+      if (i_tlog[i] >= N) return SWIM_EINVAL;
+    for (uint32_t i = 0; i < nmsg; ++i)
+      if (i_next[i] != NEVER && i_next[i] >= nmsg) return SWIM_EINVAL;
+    for (uint32_t r = 0; r < R; ++r) {  // every inbound list ends within nmsg links
+      uint32_t q = i_head[r], n = 0;
+      if (q != NEVER && q >= nmsg) return SWIM_EINVAL;
+      for (; q != NEVER && n <= nmsg; ++n) q = i_next[q];
+      if (q != NEVER) return SWIM_EINVAL;
+    }
+  }
+  // the shipped chunks of every received payload lie in the receive buffer, 16-B aligned (diff_fetch loads 16 B)
+  for (uint32_t ri = 0; ri < nrx; ++ri) {
+    uint64_t cnt = 0;
+    for (uint32_t q = 0; q < MW; ++q) {
+      const uint64_t m = i_rxm[(size_t)ri * MW + q];
+      const uint32_t top = NCHUNK - 64 * q >= 64 ? 64 : NCHUNK - 64 * q;
+      if (top < 64 && (m >> top)) return SWIM_EINVAL;
+      cnt += (uint64_t)__builtin_popcountll(m);
+    }
+    if ((i_rxo[ri] & 15u) || i_rxo[ri] > 4ull * CH * nship || i_rxo[ri] + 4ull * CH * cnt > 4ull * CH * nship) return SWIM_EINVAL;
+  }
+
+  // ---- the Dev: only the fields k_sync_diff and k_ack_resolve (and their launchers) read ----
+  PrimBufs bf;
+  Dev d;
+  memset(&d, 0, sizeof d);
+  d.N = N, d.NS = NS, d.NS8 = NS8, d.NCHUNK = NCHUNK, d.NMETA = NMETA, d.MW = MW;
+  d.W = sharded ? 2u : 1u, d.lo = lo, d.hi = lo + R, d.NL = R;
+  d.MSGCAP = MSGCAP, d.POOLCAP = POOLCAP, d.ARENA_ROWS = AR;
+  d.ackres = lister ? (ACKRES_ON | (dirty ? ACKRES_DIRTY : 0u)) : lists ? ACKRES_ON : 0u;
+  d.rowk = bf.get<uint32_t>(w_rows, i_rows, w_rows);
+  if (k8) {
+    std::vector<uint8_t> r8((size_t)R * NS8, 0), b8(NS8, 0);
+    for (uint32_t r = 0; r < R; ++r)
+      for (uint32_t s = 0; s < NS; ++s) r8[(size_t)r * NS8 + s] = key8(i_rows[(size_t)r * NS + s]);
+    d.rowk8 = bf.get<uint8_t>(r8.size(), r8.data(), r8.size());
+    if (sharded) {
+      for (uint32_t s = 0; s < NS; ++s) b8[s] = key8(i_base[s]);
+      d.base_row8 = bf.get<uint8_t>(NS8, b8.data(), NS8);
+    }
+  }
+  const size_t nms = std::max<size_t>(R, (size_t)NPER * nit);  // indexed by member (dirty) and by chunk (cstat)
+  if (!sharded) {
+    std::vector<MS> ms(nms);
+    memset(ms.data(), 0, sizeof(MS) * nms);
+    for (uint32_t r = 0; r < R; ++r)
+      for (uint32_t q = 0; q < MSW; ++q) ms[r].dirty[q] = i_dirty[(size_t)r * MSW + q];
+    d.ms = bf.get<MS>(nms, ms.data(), nms);
+  }
+  {
+    std::vector<SyncMsg> mv(nmsg ? nmsg : 1);
+    memset(mv.data(), 0, sizeof(SyncMsg) * mv.size());
+    for (uint32_t i = 0; i < nmsg; ++i) {
+      const uint32_t* m = i_msgs + 6ull * i;
+      mv[i].src = m[0], mv[i].dst = m[1], mv[i].kind = m[2], mv[i].payload = m[3], mv[i].pin = m[4], mv[i].tln = m[5];
+    }
+    d.msgs[b] = bf.get<SyncMsg>(MSGCAP, mv.data(), nmsg);
+    uint32_t nm[2] = {0, 0};
+    nm[b] = nmsg;
+    d.nmsg = bf.get<uint32_t>(2, nm, 2);
+  }
+  d.arena[b] = bf.get<uint32_t>(w_arena, i_arena, w_arena);
+  std::vector<uint32_t> fill(std::max<uint64_t>({2ull * (POOLCAP + 64), 2ull * MSGCAP * NMETA, 4 * ncap, 4ull * MSGCAP, 2ull * N}), sent);
+  d.pool = bf.get<uint64_t>(POOLCAP + 64, fill.data(), POOLCAP + 64);
+  d.chunk_meta = bf.get<uint32_t>(2ull * MSGCAP * NMETA, fill.data(), 2ull * MSGCAP * NMETA);
+  d.dlist = bf.get<uint32_t>(4 * ncap, fill.data(), 4 * ncap);
+  d.dlist_w = bf.get<uint32_t>(4ull * MSGCAP, fill.data(), 4ull * MSGCAP);
+  d.ndl = bf.get<uint32_t>(1, &nnar, 1);
+  d.ndlw = bf.get<uint32_t>(1, &nwide, 1);
+  d.pool_used = bf.get<uint32_t>(1);
+  d.err = bf.get<uint32_t>(8);
+  d.ctr = bf.get<unsigned long long>(32);
+  d.ctr_sh = bf.get<unsigned long long>((size_t)CSH * CSTRIDE);
+  d.halt = (uint32_t*)(d.ctr_sh + SH_HALT);
+  d.hflag = bf.get<uint32_t>(HF_BYTES / 4);
+  if (lister) {
+    d.tl_tick = bf.get<uint32_t>(2ull * R, i_tick, 2ull * R);
+    d.tl_n = bf.get<uint32_t>(2ull * R, i_tln, 2ull * R);
+    d.tlog = bf.get<uint32_t>(2ull * R * TL, i_tlog, 2ull * R * TL);
+    std::fill(fill.begin(), fill.end(), NEVER);
+    d.m_head = bf.get<uint32_t>(2ull * N, fill.data(), 2ull * N);
+    d.m_next = bf.get<uint32_t>(2ull * MSGCAP, fill.data(), 2ull * MSGCAP);
+    if (bf.rc == SWIM_OK && (hipMemcpy(d.m_head + (size_t)b * N, i_head, 4ull * R, hipMemcpyHostToDevice) != hipSuccess ||
+                             (nmsg && hipMemcpy(d.m_next + (size_t)b * MSGCAP, i_next, 4ull * nmsg, hipMemcpyHostToDevice) != hipSuccess)))
+      bf.rc = SWIM_EDEVICE;
+  }
+  if (sharded) {
+    d.rx_mask = bf.get<uint64_t>((size_t)MW * nrx, i_rxm, (size_t)MW * nrx);
+    d.rx_off = bf.get<uint64_t>(nrx, i_rxo, nrx);
+    d.base_row = bf.get<uint32_t>(NS, i_base, NS);
+    d.xa_recv = bf.get<uint8_t>(4ull * CH * nship, i_ship, 4ull * CH * nship);
+  }
+  if (bf.rc == SWIM_OK && (nnar + nwide) &&
+      (hipMemcpy(d.dlist, i_nar, 16ull * nnar, hipMemcpyHostToDevice) != hipSuccess ||
+       hipMemcpy(d.dlist_w, i_wide, 16ull * nwide, hipMemcpyHostToDevice) != hipSuccess))
+    bf.rc = SWIM_EDEVICE;
+  Dev* self = bf.get<Dev>(1);
+  d.self = self;
+  if (bf.rc == SWIM_OK && hipMemcpy(self, &d, sizeof d, hipMemcpyHostToDevice) != hipSuccess) bf.rc = SWIM_EDEVICE;
+  if (bf.rc != SWIM_OK) return bf.rc;
+
+  if (lister)
+    launch_diff(d, k, nullptr, nullptr, ls, grid);
+  else
+    launch_diff_listed(d, k, nullptr, grid);
+  if (!bf.ran()) return bf.rc;
+
+  // ---- results ----
+  uint32_t* o = out;
+  bf.back(o, d.pool, 8ull * (POOLCAP + 64));
+  o += 2ull * (POOLCAP + 64);
+  {
+    unsigned long long c[32], pind = 0;
+    static const uint32_t order[10] = {C_DIFFMSG, C_DIFFMSG_ALL, C_DIFFWIDE, C_DIFFWIDE_ALL, C_ACKRES, C_ACKRES_ALL,
+                                       C_DSTREAM, C_DSUBJ,       C_DSUBJ_ALL, C_DMSGSKIP};
+    if (bf.back(c, d.ctr, sizeof c) && bf.back(&pind, d.ctr_sh + SH_PINDEC, 8)) {
+      unsigned long long r[12] = {0};
+      for (int i = 0; i < 10; ++i) r[i] = c[order[i]];
+      r[10] = pind;
+      memcpy(o, r, sizeof r);
+    }
+    o += 24;
+  }
+  {
+    std::vector<MS> ms(d.ms ? nms : 0);
+    if (d.ms) bf.back(ms.data(), d.ms, sizeof(MS) * nms);
+    for (uint32_t c = 0; c < NCHUNK; ++c) {
+      unsigned long long cs[3] = {0, 0, 0};
+      if (d.ms) memcpy(cs, ms[c].cstat, sizeof cs);
+      memcpy(o + 6ull * c, cs, sizeof cs);
+    }
+    o += 6ull * NCHUNK;
+  }
+  bf.back(o, d.chunk_meta, 8ull * NMETA * nmsg);
+  o += 2ull * NMETA * nmsg;
+  {
+    std::vector<SyncMsg> mv(nmsg ? nmsg : 1);
+    bf.back(mv.data(), d.msgs[b], sizeof(SyncMsg) * nmsg);
+    for (uint32_t i = 0; i < nmsg; ++i) o[3ull * i] = mv[i].kind, o[3ull * i + 1] = mv[i].ncand, o[3ull * i + 2] = mv[i].pin;
+    o += 3ull * nmsg;
+  }
+  bf.back(o, d.arena[b], 4 * w_arena);
+  o += w_arena;
+  bf.back(o, d.dlist, 16 * ncap);
+  o += 4 * ncap;
+  bf.back(o, d.dlist_w, 16ull * MSGCAP);
+  o += 4ull * MSGCAP;
+  bf.back(o, d.pool_used, 4);
+  bf.back(o + 1, d.err, 4);
+  bf.back(o + 2, d.ndl, 4);
+  bf.back(o + 3, d.ndlw, 4);
+  bf.back(o + 4, d.halt, 4 * HALT_WORDS);
+  bf.back(o + 7, d.hflag + HF_STREAMED, 4);
+  return bf.rc;
+}
+
 }  // namespace
 }  // namespace swim
 
 extern "C" int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t n_params, const void* in, size_t in_bytes,
                                     void* out, size_t out_bytes, uint32_t device) {
   using namespace swim;
-  if (op > SWIM_PRIM_RING_MOVE || !params || n_params > 8 || !out || (in_bytes && !in) || ((uintptr_t)in & 7u) ||
+  if (op > SWIM_PRIM_SYNC_DIFF || !params || n_params > 16 || !out || (in_bytes && !in) || ((uintptr_t)in & 7u) ||
       ((uintptr_t)out & 7u))
     return SWIM_EINVAL;
   int ndev = 0;
@@ -434,6 +665,7 @@ extern "C" int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t 
     case SWIM_PRIM_DIRTY: return prim_dirty(params, n_params, i32, in_bytes, o32, out_bytes);
     case SWIM_PRIM_ARITH: return prim_arith(params, n_params, i32, in_bytes, o32, out_bytes);
     case SWIM_PRIM_FEISTEL: return prim_feistel(params, n_params, in_bytes, o32, out_bytes);
-    default: return prim_ring_move(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_RING_MOVE: return prim_ring_move(params, n_params, i32, in_bytes, o32, out_bytes);
+    default: return prim_sync_diff(params, n_params, i32, in_bytes, o32, out_bytes);
   }
 }

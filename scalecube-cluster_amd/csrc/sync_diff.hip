@@ -762,9 +762,11 @@ static uint32_t diff_grid() {
 
 // a timed launch carries its start / stop events in its own dispatch (hipExtLaunchKernelGGL): the interval is the
 // kernel's, not that of two marker packets around it (those read ~4 us per launch longer than rocprofv3)
+// grid_arg: 0 = that grid (every engine launch); the known-answer tests pass their own (swim_debug_prim_eval)
 static void launch_sync_diff(const Dev& d, uint32_t b, hipStream_t st, uint32_t timed, uint32_t spec = 0,
-                             const TickEvents* prof = nullptr) {
-  static const uint32_t grid = diff_grid();
+                             const TickEvents* prof = nullptr, uint32_t grid_arg = 0) {
+  static const uint32_t own = diff_grid();
+  const uint32_t grid = grid_arg ? grid_arg : own;
   if (prof) {
     hipEvent_t e0 = (hipEvent_t)prof->ev[0], e1 = (hipEvent_t)prof->ev[1];
     if (d.W > 1)
@@ -794,15 +796,15 @@ static void launch_ack_resolve(const Dev& d, uint32_t k, hipStream_t st, uint32_
   hipLaunchKernelGGL(k_ack_resolve, dim3(128), dim3(512), 0, st, ra, k, ls, timed ? 1u : 0u);
 }
 
-void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof, uint32_t ls) {
+void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof, uint32_t ls, uint32_t grid) {
   hipStream_t st = (hipStream_t)stream;
   if (!diff_elidable(d)) ls &= ~LS_NODIFF;
   launch_ack_resolve(d, k, st, ls, prof != nullptr);
-  if (k > 0 && !(ls & LS_NODIFF)) launch_sync_diff(d, (k - 1) & 1, st, prof ? 1u : 0u, ls & LS_SPEC, prof);
+  if (k > 0 && !(ls & LS_NODIFF)) launch_sync_diff(d, (k - 1) & 1, st, prof ? 1u : 0u, ls & LS_SPEC, prof, grid);
 }
 
-void launch_diff_listed(const Dev& d, uint32_t k, void* stream) {
-  if (k > 0) launch_sync_diff(d, (k - 1) & 1, (hipStream_t)stream, 0u);
+void launch_diff_listed(const Dev& d, uint32_t k, void* stream, uint32_t grid) {
+  if (k > 0) launch_sync_diff(d, (k - 1) & 1, (hipStream_t)stream, 0u, 0u, nullptr, grid);
 }
 
 }  // namespace swim

@@ -251,7 +251,10 @@ DEBUG_SIGNATURES = {
                                        C.c_uint32]),
 }
 # swim_debug_prim_eval: ops, and the sub-ops of PRIM_WAVE and PRIM_ARITH (include/swimhip_debug.h has the layouts)
-(PRIM_SCAN, PRIM_SEG_SORT, PRIM_ROUTING, PRIM_WAVE, PRIM_DIRTY, PRIM_ARITH, PRIM_FEISTEL, PRIM_RING_MOVE) = range(8)
+(PRIM_SCAN, PRIM_SEG_SORT, PRIM_ROUTING, PRIM_WAVE, PRIM_DIRTY, PRIM_ARITH, PRIM_FEISTEL, PRIM_RING_MOVE,
+ PRIM_SYNC_DIFF) = range(9)
+# PRIM_SYNC_DIFF's flags (SWIM_PRIM_SD_*)
+(SD_K8, SD_LISTER, SD_LISTS, SD_SHARDED, SD_DIRTY) = (1, 2, 4, 8, 16)
 (WAVE_APPEND, WAVE_RESERVE, WAVE_BLOCK_RESERVE, WAVE_SUM32, WAVE_MIN32, WAVE_SUM64) = range(6)
 (ARITH_DIV_GT, ARITH_S16, ARITH_RG, ARITH_KEY8, ARITH_DELAY, ARITH_EPOCH, ARITH_PAYKEY) = range(7)
 

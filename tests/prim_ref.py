@@ -487,3 +487,269 @@ def ring_ref(rg, rhead, rtail, B2):
             out[m, p % B2] = rg[m, p % B]
             p = (p + 1) & M32
     return out
+
+
+# ---------------------------------------------------------------------------------------------- SYNC diff and lister
+# References for k_sync_diff and k_ack_resolve (tests/test_gpu_sync_diff.py, SWIM_PRIM_SYNC_DIFF). A key is
+# inc << 2 | status (status 0 = ABSENT); a candidate word is subject << 34 | status << 32 | inc.
+MCH, TL, NPER, PINWALK = 1024, 16, 4, 8
+KF_DEFER, KF_ABS, KF_RES = 0x100, 0x200, 0x400
+PAY_RX, DESC_PIN, DESC_DEFER = 0x40000000, 0x80000000, 0xFFFFFFFE
+E_POOL = 128
+SD_K8, SD_LISTER, SD_LISTS, SD_SHARDED, SD_DIRTY = 1, 2, 4, 8, 16
+LS_SPEC, LS_NODIFF = 1, 2
+SD_SENT = 0xA5A5A5A5
+SD_SENT64 = SD_SENT | SD_SENT << 32
+SD_NS = [1000, 1025, 2048, 2049, 2056, 8192, 8200, 131080, 262152]
+SD_CTR = ["diffmsg", "diffmsg_all", "diffwide", "diffwide_all", "ackres", "ackres_all", "dstream", "dsubj", "dsubj_all",
+          "dmsgskip", "pindec", "spare"]
+
+
+def sd_sizes(N):
+    """The sizes swim_create derives from the member count."""
+    NS, NS8 = -(-N // 8) * 8, -(-N // 16) * 16
+    NCHUNK, NMETA = -(-NS // CH), -(-NS // MCH)
+    return dict(N=N, NS=NS, NS8=NS8, NCHUNK=NCHUNK, NMETA=NMETA, MW=-(-NCHUNK // 64), nit=-(-NCHUNK // NPER))
+
+
+def key34(k):
+    k = np.asarray(k).astype(np.uint64)
+    return (k >> np.uint64(2)) | ((k & np.uint64(3)) << np.uint64(32))
+
+
+def sync_diff_ref(payload_keys, receiver_keys):
+    """(segments, absent): for each 1024-subject segment the words subject << 34 | key34(key), in subject order, of the
+    payload records that are present and unequal to the receiver's; absent: some subject is ABSENT in the payload and
+    present in the receiver (KF_ABS)."""
+    p, r = np.asarray(payload_keys, np.uint32), np.asarray(receiver_keys, np.uint32)
+    assert p.shape == r.shape
+    present = (p & 3) != 0
+    subj = np.flatnonzero(present & (p != r))
+    words = (subj.astype(np.uint64) << np.uint64(34)) | key34(p[subj])
+    nseg = -(-len(p) // MCH)
+    cut = np.searchsorted(subj, np.arange(nseg + 1) * MCH)
+    return [words[cut[g]:cut[g + 1]] for g in range(nseg)], bool((~present & ((r & 3) != 0)).any())
+
+
+def rx_payload(base, mask, shipped):
+    """A payload received from another shard: the baseline row overlaid with the shipped chunks, which are the chunks
+    whose mask bit is set, in ascending chunk order. shipped: uint32[popcount(mask)][CH]."""
+    out = np.array(base, np.uint32)
+    j = 0
+    for c in range(-(-len(out) // CH)):
+        if (mask >> c) & 1:
+            n = min(CH, len(out) - c * CH)
+            out[c * CH:c * CH + n] = shipped[j][:n]
+            j += 1
+    assert j == bin(mask).count("1") == len(shipped)
+    return out
+
+
+def sd_payload(case, m):
+    """The keys of message m's payload (NS of them): the sender's live row (pinned or not), its arena snapshot, or a
+    received payload."""
+    pay = m["payload"]
+    if pay == NEVER:
+        return case["rows"][m["src"] - case.get("lo", 0)]
+    if pay & PAY_RX:
+        rx = case["rx"][pay & ~PAY_RX]
+        return rx_payload(case["base"], rx["mask"], rx["chunks"])
+    return case["arena"][pay]
+
+
+def sd_msg(src, dst, kind=1, payload=NEVER, pin=NEVER, tln=0):
+    return dict(src=src, dst=dst, kind=kind, payload=payload, pin=pin, tln=tln)
+
+
+def desc_pay(m):
+    """Where a list entry says the payload is (engine.h DESC_*)."""
+    if m["kind"] & KF_DEFER:
+        return DESC_DEFER
+    if m["payload"] != NEVER:
+        return m["payload"]
+    return NEVER if m["pin"] == NEVER else DESC_PIN | m["pin"]
+
+
+def sd_log_subjects(case, m):
+    """The subjects only which a SYNC_ACK's payload and its receiver's row can differ in when the ACK is resolvable: the
+    responder's log prefix of tick k - 1 and the requester's logs of ticks k - 2 and k - 1; None when not resolvable
+    (k < 2, no KF_RES, delayed, pinned, or a log past TL)."""
+    k = case["k"]
+    if k < 2 or not m["kind"] & KF_RES or m["kind"] & KF_DEFER or m["pin"] != NEVER or m["tln"] > TL:
+        return None
+    p0, p1, dst, src = k & 1, (k - 1) & 1, m["dst"], m["src"]
+    n0 = int(case["tl_n"][p0][dst]) if int(case["tl_tick"][p0][dst]) == k - 2 else 0
+    n1 = int(case["tl_n"][p1][dst]) if int(case["tl_tick"][p1][dst]) == k - 1 else 0
+    if n0 > TL or n1 > TL:
+        return None
+    return sorted(set(case["tlog"][p1][src][:m["tln"]].tolist()) | set(case["tlog"][p0][dst][:n0].tolist())
+                  | set(case["tlog"][p1][dst][:n1].tolist()))
+
+
+def inbound_list(case, dst):
+    out, q = [], int(case["m_head"][dst])
+    while q != NEVER:
+        out.append(q)
+        q = int(case["m_next"][q])
+    return out
+
+
+def pin_clean_ref(case, i, dst):
+    """A pinned live-row payload is decided from the masks when its receiver's inbound list has at most PINWALK messages,
+    holds the message, all of them carry live rows and none is delayed, and the receiver's and every sender's masks are
+    clear."""
+    lst, MW = inbound_list(case, dst), sd_sizes(case["N"])["MW"]
+    if len(lst) > PINWALK or i not in lst:
+        return False
+    msgs = [case["msgs"][q] for q in lst]
+    if any(m["payload"] != NEVER or m["kind"] & KF_DEFER for m in msgs):
+        return False
+    return not any(int(case["dirty"][r][w]) for r in [dst] + [m["src"] for m in msgs] for w in range(MW))
+
+
+def ack_resolve_ref(case):
+    """What k_ack_resolve does with each message of a one-GPU case, by the documented conditions: a list of dicts with
+    how = "resolved" (cand: the candidate words among the de-duplicated log subjects, in subject order), "pin" (a pinned
+    live row decided from the masks), "decided" (a narrow payload with no chunk to stream), "narrow" (items: {item:
+    chunk bits}) or "wide" (place: the entry's fourth word)."""
+    z = sd_sizes(case["N"])
+    k8, masks = bool(case["flags"] & SD_K8), bool(case["flags"] & SD_DIRTY)
+    out = []
+    for i, m in enumerate(case["msgs"]):
+        subs = sd_log_subjects(case, m)
+        if subs is not None:
+            p, r = sd_payload(case, m), case["rows"][m["dst"]]
+            c = [s for s in subs if p[s] & 3 and p[s] != r[s]]
+            out.append(dict(how="resolved", cand=[(s << 34) | int(key34(p[s])) for s in c]))
+            continue
+        pw = desc_pay(m)
+        if k8 and masks and m["payload"] == NEVER and pw not in (NEVER, DESC_DEFER) and pin_clean_ref(case, i, m["dst"]):
+            out.append(dict(how="pin"))
+        elif k8 and pw == NEVER:
+            items = {}
+            for c in range(z["NCHUNK"]):
+                need = not masks or ((int(case["dirty"][m["src"]][c >> 6]) | int(case["dirty"][m["dst"]][c >> 6])) >> (c & 63)) & 1
+                if need:
+                    items[c // NPER] = items.get(c // NPER, 0) | 1 << (c % NPER)
+            out.append(dict(how="narrow", items=items) if items else dict(how="decided"))
+        else:
+            out.append(dict(how="wide", place=pw))
+    return out
+
+
+def sd_pack(case):
+    """(params, in words, out words) of a SWIM_PRIM_SYNC_DIFF call (include/swimhip_debug.h). MSGCAP defaults to one
+    more than the messages: the buffer's last entry stays unused, as in an engine that is not at capacity."""
+    z = sd_sizes(case["N"])
+    fl, R, msgs = case["flags"], len(case["rows"]), case["msgs"]
+    MSGCAP = case.get("MSGCAP", len(msgs) + 1)
+    arena = case.get("arena", np.zeros((0, z["NS"]), np.uint32))
+    nar, wide = case.get("narrow", []), case.get("wide", [])
+    rx = case.get("rx", [])
+    parts = [np.asarray(case.get("dirty", np.zeros((R, 3), np.uint64)), np.uint64)]
+    if fl & SD_SHARDED:
+        parts.append(np.array([[(r["mask"] >> (64 * q)) & M64 for q in range(z["MW"])] for r in rx], np.uint64).reshape(-1))
+        parts.append(np.array([r["off"] for r in rx], np.uint64))
+    parts += [u32(case["rows"]), u32(arena)]
+    parts.append(u32([[m[f] for f in ("src", "dst", "kind", "payload", "pin", "tln")] for m in msgs]).reshape(-1))
+    if fl & SD_LISTS:
+        parts.append(u32(list(nar) + list(wide)).reshape(-1))
+    if fl & SD_LISTER:
+        parts += [u32(case["tl_tick"]), u32(case["tl_n"]), u32(case["tlog"]), u32(case["m_head"]), u32(case["m_next"])]
+    if fl & SD_SHARDED:
+        parts += [u32(case["base"]), u32(case["recv"])]
+    inp = np.frombuffer(b"".join(np.ascontiguousarray(a).tobytes() for a in parts), dtype=np.uint32).copy()
+    ncap = MSGCAP if fl & SD_SHARDED else MSGCAP * z["nit"]
+    POOLCAP = case["POOLCAP"]
+    nout = (2 * (POOLCAP + 64) + 24 + 6 * z["NCHUNK"] + 2 * z["NMETA"] * len(msgs) + 3 * len(msgs) + arena.size + 4 * ncap
+            + 4 * MSGCAP + 8)
+    params = [case["N"], R, fl, len(msgs), MSGCAP, len(arena), POOLCAP, case["k"], case.get("grid", 0), SD_SENT,
+              len(nar), len(wide), case.get("lo", 0), len(rx), case.get("ls", 0)]
+    return params, inp, np.zeros(nout, np.uint32)
+
+
+def sd_unpack(case, out):
+    z = sd_sizes(case["N"])
+    n, MSGCAP = len(case["msgs"]), case.get("MSGCAP", len(case["msgs"]) + 1)
+    A = len(case.get("arena", []))
+    ncap = MSGCAP if case["flags"] & SD_SHARDED else MSGCAP * z["nit"]
+    pos = [0]
+
+    def take(words, dtype=np.uint32):
+        a = out[pos[0]:pos[0] + words]
+        pos[0] += words
+        return a.view(dtype)
+
+    r = dict(pool=take(2 * (case["POOLCAP"] + 64), np.uint64))
+    r["ctr"] = dict(zip(SD_CTR, (int(v) for v in take(24, np.uint64))))
+    r["cstat"] = take(6 * z["NCHUNK"], np.uint64).reshape(-1, 3)
+    r["meta"] = take(2 * z["NMETA"] * n).reshape(n, z["NMETA"], 2)
+    mk = take(3 * n).reshape(n, 3)
+    r["kind"], r["ncand"], r["pin"] = mk[:, 0], mk[:, 1], mk[:, 2]
+    r["arena"] = take(A * z["NS"]).reshape(A, z["NS"])
+    r["narrow"] = take(4 * ncap).reshape(-1, 4)
+    r["wide"] = take(4 * MSGCAP).reshape(-1, 4)
+    s = take(8)
+    r.update(pool_used=int(s[0]), err=int(s[1]), nnar=int(s[2]), nwide=int(s[3]), halt=s[4:7].tolist(), streamed=int(s[7]))
+    assert pos[0] == len(out)
+    return r
+
+
+def sd_expect(case, narrow, wide):
+    """What k_sync_diff must leave for the lists it streams: per message {segment: candidate words} for the segments it
+    must write (an unlisted one stays untouched) and whether it sets KF_ABS; and per chunk the number of narrow compares
+    of it (one GPU) that found a difference or an absent record (MS::cstat[1]). narrow / wide: entries (message, sender,
+    receiver, fourth word). A narrow chunk whose bit is clear gets zero counts whatever the rows hold, a deferred
+    message zero counts everywhere."""
+    z = sd_sizes(case["N"])
+    sharded = bool(case["flags"] & SD_SHARDED)
+    exp = [dict(segs={}, absent=False) for _ in case["msgs"]]
+    lo = case.get("lo", 0)
+    differed = np.zeros(z["NCHUNK"], np.int64)
+
+    def add(i, p, r, chunks):
+        for c in chunks:
+            a, b = c * CH, min((c + 1) * CH, z["NS"])
+            segs, ab = sync_diff_ref(p[a:b], r[a:b])
+            exp[i]["absent"] |= ab
+            yield ab or any(len(w) for w in segs)
+            for g, w in enumerate(segs):
+                exp[i]["segs"][2 * c + g] = w + (np.uint64(a) << np.uint64(34))
+
+    for i, src, dst, w in wide:
+        r = case["rows"][dst - lo]
+        if w == DESC_DEFER:
+            for g in range(z["NMETA"]):
+                exp[i]["segs"][g] = np.zeros(0, np.uint64)
+            continue
+        if w == NEVER or w & DESC_PIN:
+            p = case["rows"][src - lo]
+        elif w & PAY_RX:
+            rx = case["rx"][w & ~PAY_RX]
+            p = rx_payload(case["base"], rx["mask"], rx["chunks"])
+        else:
+            p = case["arena"][w]
+        list(add(i, p, r, range(z["NCHUNK"])))
+    for i, src, dst, w in narrow:
+        r = case["rows"][dst - lo]
+        if sharded:
+            if w == NEVER:
+                p = case["rows"][src - lo]
+            else:
+                rx = case["rx"][w & ~PAY_RX]
+                p = rx_payload(case["base"], rx["mask"], rx["chunks"])
+            list(add(i, p, r, range(z["NCHUNK"])))
+            continue
+        t, m4 = w >> 4, w & 15
+        p = case["rows"][src - lo]
+        for j in range(NPER):
+            c = NPER * t + j
+            if c >= z["NCHUNK"]:
+                break
+            if (m4 >> j) & 1:
+                differed[c] += list(add(i, p, r, [c]))[0]
+            else:
+                for g in (2 * c, 2 * c + 1):
+                    if g < z["NMETA"]:
+                        exp[i]["segs"][g] = np.zeros(0, np.uint64)
+    return exp, differed

@@ -6,8 +6,9 @@ oracle, and the masks' invariant (a clean chunk equals the baseline's) must hold
 
 Sizes sit just past the chunk (2048 subjects) and item (4 chunks) boundaries: 2 100 members are 2 chunks, 4 200 are 3
 (the last one partial), 9 000 are 5: one full item and a second one with a single partial chunk. A second mask word
-needs more than 131 072 members: the lister's and k_sync_diff's MW > 1 loops are not covered here (the helpers they
-call, dirty_mark, dirty_mark_wave and payload_key_at's rank, run on 2- and 3-word masks in test_gpu_primitives.py)."""
+needs more than 131 072 members, which no cluster here has: the lister's and k_sync_diff's MW > 1 loops run on rows of
+131 080 and 262 152 subjects (two and three mask words) in test_gpu_sync_diff.py, the helpers they call (dirty_mark,
+dirty_mark_wave and payload_key_at's rank) on 2- and 3-word masks in test_gpu_primitives.py."""
 import os
 
 import numpy as np

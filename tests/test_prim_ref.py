@@ -325,3 +325,168 @@ def test_ring_inputs_and_ref(B, B2):
         assert (want[m] != R.RING_SENTINEL).sum() == len(held)
         for p in held:
             assert want[m, p & (B2 - 1)] == rg[m, p & (B - 1)]
+
+
+# ---------------------------------------------------------------------------------------------- SYNC diff and lister
+def naive_diff(p, r):
+    """Subject by subject, in Python integers."""
+    segs, absent = [[] for _ in range(-(-len(p) // R.MCH))], False
+    for s, (a, b) in enumerate(zip(p.tolist(), r.tolist())):
+        if a & 3 == 0:
+            absent |= b & 3 != 0
+        elif a != b:
+            segs[s // R.MCH].append((s << 34) | (a & 3) << 32 | a >> 2)
+    return segs, absent
+
+
+def test_sync_diff_sizes():
+    want = {1000: (1000, 1008, 1, 1, 1, 1), 1025: (1032, 1040, 1, 2, 1, 1), 2048: (2048, 2048, 1, 2, 1, 1),
+            2049: (2056, 2064, 2, 3, 1, 1), 2056: (2056, 2064, 2, 3, 1, 1), 8192: (8192, 8192, 4, 8, 1, 1),
+            8200: (8200, 8208, 5, 9, 1, 2), 131080: (131080, 131088, 65, 129, 2, 17), 262152: (262152, 262160, 129, 257, 3, 33)}
+    assert sorted(want) == R.SD_NS
+    for N, w in want.items():
+        z = R.sd_sizes(N)
+        assert (z["NS"], z["NS8"], z["NCHUNK"], z["NMETA"], z["MW"], z["nit"]) == w, N
+    assert R.sd_sizes(3 * 64 * R.CH)["MW"] == 3 and R.sd_sizes(3 * 64 * R.CH + 1)["MW"] == 4, "three mask words: 393 216"
+
+
+def test_sync_diff_ref_against_a_subject_loop():
+    rng = np.random.default_rng(1)
+    for n in (1, 7, 1024, 1025, 2100):
+        p = R.u32(rng.integers(0, 2**32, n))
+        r = p.copy()
+        ch = rng.random(n) < 0.3
+        r[ch] = rng.integers(0, 2**32, int(ch.sum()))
+        p[rng.random(n) < 0.1] &= ~np.uint32(3)  # absent in the payload: whatever the incarnation bits say
+        r[rng.random(n) < 0.1] = 0
+        for a, b in ((p, r), (r, p), (p, p)):
+            segs, ab = R.sync_diff_ref(a, b)
+            want, wab = naive_diff(a, b)
+            assert [w.tolist() for w in segs] == want and ab == wab, n
+    segs, ab = R.sync_diff_ref(R.u32([0x401, 0xFF, 0x3FC]), R.u32([0x402, 0x1FF, 0]))
+    assert segs[0].tolist() == [1 << 32 | 0x100, 1 << 34 | 3 << 32 | 0x3F] and not ab, "the third is absent in both"
+    assert int(R.key34(0xFFFFFFFF)) == 3 << 32 | 0x3FFFFFFF
+
+
+def test_rx_payload_overlays_the_shipped_chunks_by_mask():
+    for MW, mask, subs in R.paykey_cases():
+        NS, base, ship = R.paykey_input(MW, mask)
+        pay = R.rx_payload(base, R.mask_int(mask), ship)
+        assert np.array_equal(pay[subs], R.paykey_ref(mask, subs)), "the same answers as payload_key_at's reference"
+    base = np.arange(2 * R.CH + 8, dtype=np.uint32)  # a partial last chunk
+    pay = R.rx_payload(base, 0b101, [np.full(R.CH, 7, np.uint32), np.full(R.CH, 9, np.uint32)])
+    assert (pay[:R.CH] == 7).all() and np.array_equal(pay[R.CH:2 * R.CH], base[R.CH:2 * R.CH]) and (pay[2 * R.CH:] == 9).all()
+
+
+def sd_cases():
+    import test_gpu_sync_diff as G  # the GPU tests' case builders (importing it touches no GPU)
+    return G
+
+
+def test_sync_diff_cases_meet_their_preconditions():
+    G = sd_cases()
+    for N in R.SD_NS:
+        z = R.sd_sizes(N)
+        rows = G.rows_for(N)
+        assert rows.shape == (8, z["NS"]) and (rows[:, N:] == 0).all(), "padding keys are absent"
+        assert ((rows[0, :N] & 3) != 0).all() and (rows[0, :N] < 0xFF).all() and ((rows[2] & 3) == 0).all()
+        d = np.flatnonzero(rows[1] != rows[0]).tolist()
+        assert d == sorted({s for s in G.EDGE_SUBJECTS + [N - 1] if s < N})
+        for r, lo, hi in ((3, 0.003, 0.02), (4, 0.4, 0.6)):
+            assert lo < (rows[r, :N] != rows[0, :N]).mean() < hi
+        big5, big6 = rows[5, :N] >= 0xFF, rows[6, :N] >= 0xFF
+        if N >= 2048:
+            assert (big5 & ~big6).any() and (big6 & ~big5).any(), "an escaped key in the payload only, the receiver only"
+            assert (big5 & big6 & (rows[5, :N] == rows[6, :N])).any() and (big5 & big6 & (rows[5, :N] != rows[6, :N])).any()
+            both = np.flatnonzero(big5 & big6 & (rows[5, :N] != rows[6, :N]))
+            assert (both % 32 == 0).any() and (both % 32 == 31).any(), "at a lane's first and last subject"
+            lanes5 = set((np.flatnonzero(big5 | big6) // 32).tolist())
+            small = np.flatnonzero((rows[5, :N] != rows[6, :N]) & ~big5 & ~big6) // 32
+            assert any(l not in lanes5 and (l - 1 in lanes5 or l + 1 in lanes5) for l in small.tolist()), \
+                "a lane that differs on shadows only next to an escaped one"
+        st = (rows[5, :N] != rows[0, :N]) & (rows[5, :N] >> 2 == rows[0, :N] >> 2)
+        assert st.any() and ((rows[5, :N][st] & 3) != 0).all(), "only the status bits differ"
+        assert ((rows[7, :N] == 0) & (rows[0, :N] != 0)).any()
+        odd = np.flatnonzero((rows[2] >= 0xFF) & (rows[7] == 0))  # an escape in the receiver only, both records absent
+        assert len(odd) == 2 and not (rows[7].reshape(-1, 8)[odd // 8] >= 0xFF).any() and not R.sync_diff_ref(rows[7], rows[2])[1]
+        case = G.listed_case(N)
+        exp, _ = R.sd_expect(case, case["narrow"], case["wide"])
+        total = sum(len(w) for e in exp for w in e["segs"].values())
+        assert 0 < total <= case["POOLCAP"] <= 2**22
+        assert any(e["absent"] for e in exp) and not all(e["absent"] for e in exp)
+        assert {w for *_, w in case["wide"]} >= {R.NEVER, R.DESC_DEFER, R.DESC_PIN | 0, 3}, "every kind of wide payload"
+        assert len({(i, w >> 4) for i, _, _, w in case["narrow"]}) == len(case["narrow"]) == 10 * z["nit"]
+        params, inp, out = R.sd_pack(case)
+        assert len(params) == 15 and inp.dtype == out.dtype == np.uint32 and len(inp) % 2 == 0
+
+
+def test_ack_resolve_ref_and_its_cases():
+    G = sd_cases()
+    seen = set()
+    for N in (2049, 8200):
+        for q in range(0, len(G.LOG_LENGTHS), 4):
+            specs = [dict(tln=a, n0=b, n1=c, where=("one", "ends")[(q + j) % 2]) for j, (a, b, c) in enumerate(G.LOG_LENGTHS[q:q + 4])]
+            case = G.log_case(N, 6 + q % 3, specs, 300 + q + N)
+            for m, sp, v in zip(case["msgs"], specs, R.ack_resolve_ref(case)):
+                subs = R.sd_log_subjects(case, m)
+                p, r = R.sd_payload(case, m), case["rows"][m["dst"]]
+                assert v["how"] == "resolved" and len(subs) <= sp["tln"] + sp["n0"] + sp["n1"] <= 3 * R.TL
+                assert set(np.flatnonzero(p != r).tolist()) <= set(subs), "resolvable: the rows differ only in logged subjects"
+                # second formulation: the full diff, which then holds only logged subjects
+                segs, _ = R.sync_diff_ref(p, r)
+                assert np.concatenate(segs).tolist() == v["cand"]
+                seen.add((sp["tln"], sp["n0"], sp["n1"], len(subs) < sp["tln"] + sp["n0"] + sp["n1"]))
+    assert {s[:3] for s in seen} == set(G.LOG_LENGTHS) and (R.TL, R.TL, R.TL, True) in seen, "with duplicates across the logs"
+    # a stale tick empties that log; the conditions that leave a message to the diff
+    case = G.log_case(8200, 9, [dict(tln=4, n0=5, n1=6, stale=0), dict(tln=4, n0=5, n1=6, stale=1)], 3)
+    n = [len(R.sd_log_subjects(case, m)) for m in case["msgs"]]
+    assert n[0] <= 4 + 6 and n[1] <= 4 + 5
+    for sp in (dict(tln=R.TL + 1, n0=0, n1=0), dict(tln=0, n0=R.TL + 1, n1=0), dict(tln=0, n0=0, n1=R.TL + 1),
+               dict(tln=1, n0=1, n1=1, kind=2), dict(tln=1, n0=1, n1=1, defer=True), dict(tln=1, n0=1, n1=1, pin=True)):
+        case = G.log_case(8200, 9, [sp], 4)
+        assert R.sd_log_subjects(case, case["msgs"][0]) is None, sp
+    assert R.sd_log_subjects(G.log_case(8200, 1, [dict(tln=1, n0=0, n1=1)], 5), dict(R.sd_msg(1, 0, kind=R.KF_RES, tln=1))) is None
+
+
+def test_mask_and_pin_cases():
+    G = sd_cases()
+    for N in (2049, 8200, 131080, 262152):
+        z = R.sd_sizes(N)
+        case = G.mask_case(N, 40 + N)
+        base = G.rows_for(N)[0]
+        words = set()
+        for r in range(8):
+            m = R.mask_int(case["dirty"][r])
+            assert m < 1 << z["NCHUNK"]
+            words |= {c >> 6 for c in range(z["NCHUNK"]) if (m >> c) & 1}
+            for c in range(z["NCHUNK"]):
+                same = np.array_equal(case["rows"][r, c * R.CH:(c + 1) * R.CH], base[c * R.CH:(c + 1) * R.CH])
+                assert same or (m >> c) & 1, "a clean chunk equals the baseline's (a dirty one may, too)"
+        assert words == set(range(z["MW"])), "dirty bits in every mask word"
+        ref = R.ack_resolve_ref(case)
+        only_src = only_dst = 0
+        for m, v in zip(case["msgs"], ref):
+            ms, md = R.mask_int(case["dirty"][m["src"]]), R.mask_int(case["dirty"][m["dst"]])
+            assert (v["how"] == "decided") == (ms | md == 0)
+            if v["how"] == "narrow":  # second formulation: the union mask cut into items
+                assert v["items"] == {t: ((ms | md) >> (4 * t)) & 15 for t in range(z["nit"]) if ((ms | md) >> (4 * t)) & 15}
+                only_src += md == 0
+                only_dst += ms == 0
+            p, r = R.sd_payload(case, m), case["rows"][m["dst"]]
+            for c in np.unique(np.flatnonzero(p != r) // R.CH).tolist():
+                assert ((ms | md) >> c) & 1, "the rows differ only in chunks the lister has streamed"
+        assert only_src and only_dst
+        for variant in G.PIN_VARIANTS:
+            for L in (1, 2, 8, 9):
+                case = G.pin_case(N, L, variant)
+                hows = [v["how"] for v in R.ack_resolve_ref(case)]
+                lst = R.inbound_list(case, 0)
+                assert len(lst) == (L - 1 if variant == "not-on-the-list" else L)
+                if variant == "clean":
+                    assert hows == (["pin"] * L if L <= R.PINWALK else ["wide"] * L)
+                elif variant == "not-on-the-list":
+                    assert hows == ["pin"] * (L - 1) + ["wide"]
+                else:
+                    assert "pin" not in hows
+                if variant.startswith("dirty"):
+                    assert [w for r in range(8) for w in range(3) if case["dirty"][r][w]] == [z["MW"] - 1]
