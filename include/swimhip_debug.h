@@ -85,7 +85,10 @@ int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc);
  * With the masks consulted and the 8-bit key plane, the lister also decides a pinned live-row payload (one of several
  * payloads of its receiver in a tick) when every row involved is clean, and speculative batches queue no k_sync_diff
  * on untimed ticks. SWIM_NO_ELIDE=1, read by swim_create, keeps a diff launch on every tick.
- * swim_debug_diff_dirty: n <= 8 entries since create; entry 4 (n > 4) costs a pass over the key plane. */
+ * Once a whole such batch has listed nothing and written nothing, no delay is set and every row is clean, the untimed
+ * ticks queue no lister either and the receivers count their messages in its place ("Round 10").
+ * SWIM_NO_LISTERFREE=1, read by swim_create, keeps the lister on every tick.
+ * swim_debug_diff_dirty: n <= 10 entries since create; entry 4 (n > 4) costs a pass over the key plane. */
 #define SWIM_DD_SKIPPED 0u      /* narrow chunks decided from the masks, not streamed */
 #define SWIM_DD_STREAMED 1u     /* narrow chunks streamed */
 #define SWIM_DD_MSG_SKIPPED 2u  /* payloads decided without streaming any chunk */
@@ -94,6 +97,8 @@ int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc);
 #define SWIM_DD_PIN_DECIDED 5u  /* pinned live-row payloads decided from the masks (among MSG_SKIPPED) */
 #define SWIM_DD_DIFF_ELIDED 6u  /* ticks run without a k_sync_diff launch (speculative batches, SWIM_NO_ELIDE: 0) */
 #define SWIM_DD_DIFF_HALTS 7u   /* batches stopped because a lister listed work for a diff that was not queued */
+#define SWIM_DD_LF_TICKS 8u     /* ticks run without a lister launch (lister-free batches, SWIM_NO_LISTERFREE: 0) */
+#define SWIM_DD_LF_STOPS 9u     /* lister-free batches stopped because a member kernel wrote */
 int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n);
 
 /* the masks' invariant, tested directly: the number of (row, chunk) pairs marked clean whose keys differ from the

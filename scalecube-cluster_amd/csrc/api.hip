@@ -50,6 +50,7 @@ int check_err(swim_handle* h) {
 
 // open a new NetworkEmulator-settings epoch that starts at the next tick to run
 int push_epoch(swim_handle* h) {
+  lf_off(h);  // (link settings: loss, partitions, delays)
   int e = h->cur_ep;
   if (h->ep_from[e] != (uint32_t)h->tick) e = (e + 1) % (int)MAX_EPOCHS;
   h->cur_ep = e;
@@ -77,6 +78,7 @@ namespace {
 
 // rebuild the device link table from the host history (fault calls are rare; the table is at most ~300 KB)
 int upload_links(swim_handle* h) {
+  lf_off(h);
   const uint32_t now = (uint32_t)h->tick, look = h->d.LOOKBACK + 2 * h->d.ping_t + 16;
   for (auto it = h->link_hist.begin(); it != h->link_hist.end();) {  // links back at default for long: forget them
     const auto& v = it->second;
@@ -239,6 +241,7 @@ int swim_join(swim_handle* h, uint32_t m, const uint32_t* seeds, uint32_t n) {
   if (h->joined.empty()) h->joined.assign(h->d.N, 0);
   if (h->joined[m]) return SWIM_EINVAL;
   h->joined[m] = 1;
+  lf_off(h);
   uint32_t sd[16], ns = 0;  // LinkedHashSet of valid ids minus self (MembershipProtocolImpl.java:160-166)
   for (uint32_t i = 0; i < n; ++i) {
     bool dup = seeds[i] >= h->d.N || seeds[i] == m;
@@ -311,6 +314,7 @@ int swim_leave(swim_handle* h, uint32_t m) {
   uint32_t dt = 0, req = 0;
   HIPCK(hipMemcpy(&dt, h->d.dead_tick + m, 4, hipMemcpyDeviceToHost));
   if (dt != NEVER) return SWIM_EINVAL;
+  lf_off(h);
   const uint32_t one = 1;  // every shard: k_gossip_apply keeps ALIVE receipts about a leaver (its DEAD may arrive in P1)
   HIPCK(h2d(h->stream, h->d.leaving + m, &one, 4));
   if (!owns(h, m)) return SWIM_OK;
@@ -331,6 +335,7 @@ int swim_set_member_config(swim_handle* h, uint32_t m, const swim_member_config*
       !to_ticks(mc->ping_interval_ms, h->cfg.tick_ms, &pt) || !to_ticks(mc->ping_timeout_ms, h->cfg.tick_ms, &tt) || pt == 0)
     return SWIM_EINVAL;
   const uint32_t v[4] = {pt, tt, mc->ping_req_members, mc->sync_group};
+  lf_off(h);
   HIPCK(hipStreamSynchronize(h->stream));
   HIPCK(h2d(h->stream, d.mcfg + 4ull * m, v, sizeof(v)));
   if (h->cfg.init_mode == SWIM_INIT_PRECONVERGED && d.mode != SWIM_MODE_RUMOR) {
@@ -403,6 +408,7 @@ int swim_set_link_loss(swim_handle* h, uint32_t src, uint32_t dst, uint32_t pct)
 // the delay index of a mean delay (0: none, or a delay that never reaches a tick); registers its threshold table
 static int delay_index(swim_handle* h, uint32_t delay_ms, uint32_t* idx) {
   std::vector<uint32_t> t;
+  lf_off(h);
   if (!delay_table(delay_ms, h->cfg.tick_ms, &t)) return fail(h, SWIM_EINVAL, "mean delay above 11 x tick_ms");
   *idx = 0;
   if (t.empty()) return SWIM_OK;  // no message can be delayed past its tick
@@ -794,6 +800,14 @@ int swim_drain_events(swim_handle* h, swim_event* out, size_t cap, size_t* n_out
   return SWIM_OK;
 }
 
+// the lister's counts of the ticks that ran without a lister launch (engine.h SH_LF), from the counter rows `sh`:
+// messages resolved, narrow messages decided without a stream, of those pinned
+static void lf_counts(const std::vector<unsigned long long>& sh, unsigned long long (&v)[3]) {
+  v[0] = v[1] = v[2] = 0;
+  for (uint32_t r = 0; r < CSH; ++r)
+    for (uint32_t i = 0; i < 3; ++i) v[i] += sh[(size_t)r * CSTRIDE + SH_LF + i];
+}
+
 int swim_counters_get(swim_handle* h, swim_counters* out) {
   if (!h || !out) return SWIM_EINVAL;
   if (h->grp) {  // the shards' shares summed (the tick is common)
@@ -817,6 +831,10 @@ int swim_counters_get(swim_handle* h, swim_counters* out) {
     HIPCK(hipMemcpy(sh.data(), h->d.ctr_sh, 8 * sh.size(), hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < CSH; ++r)
       for (uint32_t i = 0; i < 8; ++i) c[i] += sh[(size_t)r * CSTRIDE + i];
+    unsigned long long lf[3];
+    lf_counts(sh, lf);
+    c[C_ACKRES_ALL] += lf[0];
+    c[C_DIFFMSG_ALL] += lf[1];
   }
   std::memset(out, 0, sizeof(*out));
   out->tick = h->tick;
@@ -936,17 +954,26 @@ int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc) {
   uint32_t k = 0;
   HIPCK(hipMemcpy(&k, d.rowk + lidx(d, m) * d.NS + m, 4, hipMemcpyDeviceToHost));
   launch_key_set(d, m, m, (inc << 2) | (k & 3u), h->stream);  // (the key, its shadow and the row's dirty mask)
+  lf_off(h);  // a row no longer equals the baseline: the lister's verdict is no constant
   HIPCK(hipStreamSynchronize(h->stream));
   return SWIM_OK;
 }
 
 int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n) {
-  if (!h || !out || n > 8) return SWIM_EINVAL;
+  if (!h || !out || n > 10) return SWIM_EINVAL;
   if (h->grp || h->d.W > 1 || !h->d.MW) return SWIM_EUNSUPPORTED;
   const Dev& d = h->d;
   HIPCK(hipStreamSynchronize(h->stream));
   unsigned long long c[C_NCTR];
   HIPCK(hipMemcpy(c, d.ctr, sizeof(c), hipMemcpyDeviceToHost));
+  unsigned long long lf[3];
+  {  // what the receivers counted in the lister's place
+    std::vector<unsigned long long> sh((size_t)CSH * CSTRIDE);
+    HIPCK(hipMemcpy(sh.data(), d.ctr_sh, 8 * sh.size(), hipMemcpyDeviceToHost));
+    lf_counts(sh, lf);
+    c[C_DIFFMSG_ALL] += lf[1];
+    c[C_DMSGSKIP] += lf[1];
+  }
   // every narrow payload (listed or decided by the lister) has NCHUNK chunks: streamed or skipped
   const unsigned long long narrow = c[C_DIFFMSG_ALL] - std::min(c[C_DIFFMSG_ALL], c[C_DIFFWIDE_ALL]);
   uint32_t viol = 0;
@@ -955,8 +982,8 @@ int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n) {
   if (n > SWIM_DD_DIRTY_ROWS && (rc = dirty_check(h, &viol, &dirty)) != SWIM_OK) return rc;
   unsigned long long pindec = 0;
   HIPCK(hipMemcpy(&pindec, d.ctr_sh + SH_PINDEC, 8, hipMemcpyDeviceToHost));
-  const uint64_t v[8] = {narrow * d.NCHUNK - c[C_DSTREAM], c[C_DSTREAM], c[C_DMSGSKIP], h->rebases, dirty,
-                         pindec,         h->diff_elided, h->diff_halts};
+  const uint64_t v[10] = {narrow * d.NCHUNK - c[C_DSTREAM], c[C_DSTREAM], c[C_DMSGSKIP], h->rebases, dirty,
+                          pindec + lf[2], h->diff_elided, h->diff_halts, h->lf_ticks, h->lf_stops};
   for (size_t i = 0; i < n; ++i) out[i] = v[i];
   return SWIM_OK;
 }

@@ -92,9 +92,12 @@ constexpr uint32_t XINL = 16384;  // RCCL: bytes per peer moved by the fixed-siz
 // 8..12: SWIM_EXP & 4 (and 16..19: the gossip plane's work units per tick, for algorithmic bytes; tools/pmc_gossip.py)
 constexpr uint32_t CSH = 64, CSTRIDE = 64;  // Dev::ctr_sh rows, 512 B apart
 // a row holds 8 counters; row 0's spare words (never summed, zero at create) hold, each on a 128-B line of its own away
-// from the counters' atomics: the three halt words of the speculative batches (Dev::halt), and the pinned live-row
+// from the counters' atomics: the halt words of the speculative batches (Dev::halt), and the pinned live-row
 // payloads the lister decided from the masks (sync_diff.hip pin_clean; among C_DMSGSKIP). No allocation of their own.
-constexpr uint32_t SH_HALT = 16, SH_PINDEC = 32;
+// Every row's words SH_LF .. SH_LF + 2: what the receivers counted in the lister's place on ticks without a lister launch
+// (member.hip, lf_count): messages resolved, narrow messages decided without a stream, of those pinned; the host adds
+// them to C_ACKRES_ALL, to C_DIFFMSG_ALL and C_DMSGSKIP, and to the pinned count (api.hip lf_counts).
+constexpr uint32_t SH_LF = 8, SH_HALT = 16, SH_PINDEC = 32;
 enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29,
            // dirty-chunk skipping of the SYNC diff (one GPU): narrow 2048-subject chunks the lister had
            // streamed, their subjects over the timed and over all launches (2 B each in swim_counters.diff_key_bytes*),
@@ -526,10 +529,13 @@ void launch_init(const Dev& d, void* stream);
 void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, uint32_t ls = 0u,
                  uint32_t grid = 0u);
 void launch_diff_listed(const Dev& d, uint32_t k, void* stream, uint32_t grid = 0u);
+// one GPU with masks: halt[HALT_MASKS] = some row has a dirty chunk (cleared first)
+void launch_masks_any(const Dev& d, void* stream);
 // split: the previous tick ran the gossip plane (routed receipts for P4: k_member_tick parks the members with many,
 // k_inbox_apply runs their P4, a second k_member_tick launch their P5 and P6)
+// lf: MT_LF / MT_NOLIST for a launch of a lister-free batch (spec.h), else 0
 void launch_member(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr, bool spec = false,
-                   bool split = false);
+                   bool split = false, uint32_t lf = 0u);
 void launch_gossip(const Dev& d, uint32_t k, void* stream, const TickEvents* prof = nullptr);
 // sharded tick (W > 1): A = SYNC diff + member control + pack exchange A; B = unpack A, gossip sends, pack
 // exchange B; C = unpack B, apply receipts, routing, slot recycling. The host runs the exchanges in between and

@@ -81,6 +81,15 @@ struct swim_handle {
   uint32_t listed_seen = 0;   // Dev::halt[HALT_LISTED] as last read
   uint64_t diff_elided = 0;   // ticks run without a k_sync_diff launch (swim_debug_diff_dirty)
   uint64_t diff_halts = 0;    // batches stopped by a diff-halt
+  // the lister-free mode (step.hip spec_batch), a stricter sibling of elide_on: untimed ticks of a
+  // speculative batch queue no lister either. Entered after a whole elided batch that listed nothing and wrote nothing
+  // (Dev::halt[HALT_WROTE]) when no delay is set and every dirty mask is zero; left when a member kernel writes, when a
+  // gossip plane runs, and by every host call that touches rows, masks, messages or link settings (lf_off).
+  // SWIM_NO_LISTERFREE keeps the lister on every tick (measurements, the tests' reference path)
+  bool no_lf = getenv("SWIM_NO_LISTERFREE") != nullptr;
+  bool lf_on = false;
+  uint64_t lf_ticks = 0;  // ticks run without a lister launch (swim_debug_diff_dirty)
+  uint64_t lf_stops = 0;  // batches the wrote word stopped
   bool gossip_idle = false;  // W == 1: no gossip slot was in use after the latest member kernel
   bool gossip_ran = false;   // W == 1: the latest tick ran the gossip plane (the next P4 may have routed receipts)
   uint64_t growths = 0;      // capacity growth steps so far (grow_caps)
@@ -120,6 +129,9 @@ int dalloc(swim_handle* h, T** p, size_t count) {
   return *p ? SWIM_OK : alloc_failed(h);
 }
 inline void dfree(swim_handle* h, void* p) { h->mem.free(p); }
+
+// a host call changed something the lister's verdict depends on: the next batch queues its listers again
+inline void lf_off(swim_handle* h) { h->lf_on = false; }
 
 inline int fail(swim_handle* h, int rc, const std::string& what) {
   h->err = what;

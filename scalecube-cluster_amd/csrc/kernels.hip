@@ -229,7 +229,7 @@ void launch_init(const Dev& d, void* stream) {
   if (d.base_row) hipLaunchKernelGGL(k_init_base, dim3(cdiv(d.NS8, 256)), dim3(256), 0, st, d);
 }
 
-void launch_member(const Dev& d, uint32_t k, void* stream, const TickEvents* prof, bool spec, bool split) {
+void launch_member(const Dev& d, uint32_t k, void* stream, const TickEvents* prof, bool spec, bool split, uint32_t lf) {
   hipStream_t st = (hipStream_t)stream;
   if (prof && prof->all) hipEventRecord((hipEvent_t)prof->ev[2], st);
   if (split) {  // a gossip plane ran last tick: members with many routed receipts run P4 a wave each (k_inbox_apply)
@@ -238,7 +238,7 @@ void launch_member(const Dev& d, uint32_t k, void* stream, const TickEvents* pro
     hipLaunchKernelGGL(k_member_tick_t<BODY_RESUME>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k, MT_END);  // + tick_flag
   } else {
     hipLaunchKernelGGL(k_member_tick_t<BODY_FULL>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k,
-                       MT_END | (spec ? MT_SPEC : 0u));  // + tick_flag, or (speculative) tick_reset
+                       MT_END | (spec ? MT_SPEC | lf : 0u));  // + tick_flag, or (speculative) tick_reset
   }
   if (d.dly_on) {
     launch_sync_redeliver(d, k, st, spec);

@@ -20,8 +20,9 @@ namespace swim {
 // control path of k_member_tick this tick, and its work class: 1 = a ping and / or a periodic SYNC is due (P6) and
 // nothing else, 2 = only request-state events (ping hops, ack arrivals, timeouts), 3 = both, 0 = anything else (SYNC
 // receipt, gossip receipts or round, timers, host requests, start).
+// nolist: no lister ran for this tick (MT_NOLIST); lfc: what it would have counted for the payloads dropped here
 __device__ __forceinline__ bool member_triage(const Dev& d, uint32_t m, uint32_t k, uint32_t& cls, uint32_t& drops,
-                                              uint32_t& evs) {
+                                              uint32_t& evs, bool nolist, uint64_t& lfc) {
   // A dead member does nothing itself, but the remote hops of its in-flight requests still run at the live
   // responders (their sends fail against the dead issuer), so those hops are still evaluated for the counters.
   // every word is loaded up front (no short-circuit chain of dependent loads); the SoA loads coalesce per wave
@@ -53,7 +54,11 @@ __device__ __forceinline__ bool member_triage(const Dev& d, uint32_t m, uint32_t
     d.rc_fill[m] = 0;
     if (k > 0 && mh != NEVER) {  // dropped payloads: their pins go back to NEVER (send_sync)
       const uint32_t pb = (k - 1) & 1;
-      for (uint32_t q = mh; q != NEVER; q = d.m_next[(size_t)pb * d.MSGCAP + q]) d.msgs[pb][q].pin = NEVER;
+      for (uint32_t q = mh; q != NEVER; q = d.m_next[(size_t)pb * d.MSGCAP + q]) {
+        SyncMsg& sm = d.msgs[pb][q];
+        if (nolist) lfc += lf_count(sm.kind, sm.pin, sm.tln);
+        sm.pin = NEVER;
+      }
       d.m_head[(size_t)pb * d.N + m] = NEVER;
     }
   } else {
@@ -158,7 +163,9 @@ __device__ __forceinline__ void p0_start(ML& L, bool dead) {
 // ---- P1 SYNC / SYNC_ACK (onMessage :320-331, onSync :346-367, onSyncAck :337-343) ----
 // the senders linked this member's inbound messages into a list (head0: its head, loaded with the member's state);
 // they are handled in (src, syncSeq) order
-__device__ __forceinline__ void p1_sync(ML& L, uint32_t head0, Lap& lap) {
+// lfp: no lister ran for this tick (MT_NOLIST): where this lane adds what the lister would have counted for its
+// messages (lf_count; LDS); null otherwise
+__device__ __forceinline__ void p1_sync(ML& L, uint32_t head0, Lap& lap, uint64_t* lfp) {
   const Dev& d = *L.d;
   const uint32_t m = L.m, k = L.k;
   const uint32_t* mnext = d.m_next + (size_t)((k - 1) & 1) * d.MSGCAP;
@@ -168,13 +175,19 @@ __device__ __forceinline__ void p1_sync(ML& L, uint32_t head0, Lap& lap) {
     uint64_t key[MQ];
     uint32_t idx[MQ], n = 0;
     bool more = false;
+    uint64_t lfc = 0;
     for (uint32_t q = head; q != NEVER; q = mnext[q]) {
       if (n == d.mq_cap) {
         more = true;
         fb_add(d, FB_MQ);
+        if (lfp)  // (the rest of the list, counted only)
+          for (uint32_t r = q; r != NEVER; r = mnext[r]) lfc += lf_count(d.msgs[pb][r].kind, d.msgs[pb][r].pin, d.msgs[pb][r].tln);
         break;
       }
-      uint64_t kq = sync_order_key(d.msgs[pb][q]);
+      const SyncMsg& sq = d.msgs[pb][q];
+      uint64_t kq = sync_order_key(sq);
+      // no lister ran: the message counted as it would have (fields of the entry the key comes from: no further trip)
+      if (lfp) lfc += lf_count(sq.kind, sq.pin, sq.tln);
       uint32_t j = n++;
       while (j > 0 && key[j - 1] > kq) {
         key[j] = key[j - 1];
@@ -186,6 +199,14 @@ __device__ __forceinline__ void p1_sync(ML& L, uint32_t head0, Lap& lap) {
     }
     // (reset after the walk's loads: on gfx950 a load issued after this lane's store waits for the store)
     d.m_head[(size_t)pb * d.N + m] = NEVER;
+    // no lister ran: its decision on a pinned payload, here (a read of the pinned copy raises E_PIN, payload_key_at)
+    const bool unpinned = lfp != nullptr;
+    if (unpinned && more) {  // (a list past mq_cap: by a walk)
+      for (uint32_t q = head; q != NEVER; q = mnext[q]) d.msgs[pb][q].pin = NEVER;
+    } else if (unpinned && n > 1) {
+      for (uint32_t r = 0; r < n; ++r) d.msgs[pb][idx[r]].pin = NEVER;
+    }
+    if (lfp) *lfp += lfc;
     lap(5);
     uint64_t last = 0;
     L.trk_on = n > 1 || more;  // several payloads: later ones re-check the subjects earlier ones changed
@@ -256,7 +277,7 @@ __device__ __forceinline__ void p1_sync(ML& L, uint32_t head0, Lap& lap) {
         for (uint32_t q = 0; q < d.NW; ++q) tb[q] = 0ull;
       L.ntrk = 0;
     }
-    if (n > 1 || more)  // the pins of this tick's payloads go back to NEVER for the slots' next use (send_sync)
+    if ((n > 1 || more) && !unpinned)  // the pins of this tick's payloads go back to NEVER for the slots' next use (send_sync)
       for (uint32_t q = head; q != NEVER; q = mnext[q]) d.msgs[pb][q].pin = NEVER;
   }
 }
@@ -601,10 +622,10 @@ __device__ __forceinline__ uint32_t next_event(const ML& L) {
   return nev;
 }
 
-// One member's tick (mode: member_kernels.h). cnt: the wave's op counters, this member's added.
+// One member's tick (mode: member_kernels.h). cnt: the wave's op counters, this member's added. lfp: as p1_sync's.
 template <uint32_t mode>
 __device__ __forceinline__ void member_tick_body(const Dev& d, uint32_t m, uint32_t k, unsigned long long (&cnt)[8],
-                                                 uint4* cw, uint32_t* cw_n, bool spec) {
+                                                 uint4* cw, uint32_t* cw_n, bool spec, uint64_t* lfp) {
   const bool dead = dead_at(d, m, k);
   ML L;
   ml_init(L, d, m, k, cw, cw_n, spec);
@@ -621,7 +642,7 @@ __device__ __forceinline__ void member_tick_body(const Dev& d, uint32_t m, uint3
   if (mode != BODY_RESUME) {
     p0_host_requests(L, dead);
     p0_start(L, dead);
-    p1_sync(L, head0, lap);
+    p1_sync(L, head0, lap, lfp);
     lap(0);  // P0 + P1
     L.ev_ok = true;  // this launch walks the path list (P2) and the subscriptions (P5)
     p2_fd(L, dead, lap);
@@ -682,9 +703,11 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   const Dev& d = *dp;  // global, not kernarg: taking its address must not copy ~1 KB into per-lane scratch
   // a speculative batch halted at an earlier tick (this tick's own halt is raised while it runs), or by a diff-halt:
   // returning before tick_reset keeps the lists and the pool as the lister left them (spec.h)
-  if (mt_spec(flag) && halted_member(d.halt, k)) return;
+  if (mt_spec(flag) && halted_member(d.halt, k, mt_lf(flag))) return;
   // a speculative launch resets the next tick's counters at its start (nothing in this kernel uses them), so no block
   // waits for the last one at its end: the halt that tick_flag would raise is raised by the member taking a slot
+  // (a split tick's launches are never speculative: kernels.hip launch_member)
+  const bool spec1 = MODE == BODY_FULL && mt_spec_one_gpu(flag);
   if (mt_spec_one_gpu(flag) && blockIdx.x == 0 && threadIdx.x == 0) tick_reset(d, k);
   // SWIM_EXP & 512 (timing experiment): wall clock of each wave at entry, after triage, after its bodies, at exit
   const bool wtime = (d.exp & EXP_WAVE_CLOCK) != 0;
@@ -699,7 +722,13 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   constexpr bool resume = MODE == BODY_RESUME;  // the parked members' P5 and P6 (one lane each, from the list)
   const uint32_t m = d.lo + blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t cls = 0, drops = 0, evs = 0;
-  const bool busy = !resume && m < d.hi && member_triage(d, m, k, cls, drops, evs);
+  // no lister ran for this tick: each lane's share of the lister's counts (lf_count), from the triage and from P1 (in
+  // LDS: a register would be held across the whole body)
+  const bool nolist = MODE == BODY_FULL && mt_nolist(flag);  // (a split tick is never queued without its lister)
+  __shared__ uint64_t lfs[256];
+  uint64_t lft = 0;
+  const bool busy = !resume && m < d.hi && member_triage(d, m, k, cls, drops, evs, nolist, lft);
+  if (nolist) lfs[threadIdx.x] = lft;
   {  // the triage's record compares and folded RUMOR events, one atomic each per wave
     const uint32_t v = wave_sum(drops), e = wave_sum(evs);
     unsigned long long* cs = d.ctr_sh + (size_t)(blockIdx.x % CSH) * CSTRIDE;
@@ -746,8 +775,17 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
     unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const bool skip = ((d.exp & EXP_SKIP_CLASS0) && mcls == 0) || ((d.exp & EXP_SKIP_CLASS123) && mcls != 0);
     if (me != NEVER && !skip)
-      member_tick_body<MODE>(d, me, k, cnt, cw, &cw_n, mt_spec_one_gpu(flag));
+      member_tick_body<MODE>(d, me, k, cnt, cw, &cw_n, spec1, nolist ? &lfs[threadIdx.x] : nullptr);
     ctr_wave_add(d, cnt, lane);
+  }
+  const uint64_t lfc = nolist ? lfs[threadIdx.x] : 0ull;
+  if (nolist && __ballot(lfc != 0ull)) {  // (wave-uniform) into the block's counter row, as the op counters
+    unsigned long long* cs = d.ctr_sh + (size_t)(blockIdx.x % CSH) * CSTRIDE + SH_LF;
+#pragma unroll
+    for (uint32_t i = 0; i < 3; ++i) {
+      const uint32_t v = wave_sum((uint32_t)(lfc >> (LFC_BITS * i)) & LFC_MASK);
+      if (lane == 0 && v) atomicAdd(&cs[i], (unsigned long long)v);
+    }
   }
   if (wtime && (threadIdx.x & 63) == 0) wt[2] = wall_clock64();
   // deferred copy-on-write: the block copies each snapshot's row (final for this tick: only its member writes it),

@@ -65,9 +65,29 @@ struct ML {
   bool spec;  // a launch of a one-GPU speculative batch: a member that takes a gossip slot raises d.halt (k_member_tick)
 };
 
+// A tick without a lister launch (a lister-free batch: every row equals the baseline, both write logs k_ack_resolve
+// would read are empty, no payload is a snapshot or delayed): what the lister would have counted for
+// one message, from the fields it tests. Resolved from the (empty) write logs under res_wave's preconditions (k >= 2
+// holds in the mode); else a narrow message decided without a stream, pinned or not (pin_clean holds for every list of
+// at most PINWALK payloads: all its rows are clean). The limit of this: the lister sends the pinned payloads of a
+// longer list to the wide diff, which finds nothing in them either, and counts them there (C_DIFFWIDE_ALL, 8 B per
+// subject in diff_key_bytes, a diff-halt under elision); here they count as decided like the others. The results are
+// the same (ncand = 0 either way); those counters would differ from a run with a lister on every tick. Nine payloads
+// for one receiver in one tick of a clean steady state is a ~10^-12 event per receiver and tick at a SYNC every 10
+// ticks and rarer at the default interval.
+// Packed, LFC_BITS bits each: resolved, narrow decided, of those pinned (SH_LF's order).
+constexpr uint32_t LFC_BITS = 21, LFC_MASK = (1u << LFC_BITS) - 1u;
+__device__ __forceinline__ uint64_t lf_count(uint32_t kind, uint32_t pin, uint32_t tln) {
+  if ((kind & KF_RES) && !(kind & KF_DEFER) && pin == NEVER && tln <= TL) return 1ull;
+  return (1ull << LFC_BITS) | (pin != NEVER ? 1ull << (2 * LFC_BITS) : 0ull);
+}
+
 // a subject whose key this member's row changed in this tick, or a candidate of a payload it merged (k_ack_resolve)
+// (in a speculative batch the first entry of a tick also tells the host that this launch wrote: note_wrote, spec.h; not
+// elsewhere: 10^5 members that accept one gossip in one tick would queue as many stores at that word's L2 channel)
 __device__ __forceinline__ void tl_add(ML& L, uint32_t s) {
   if (L.ntl && L.tlast == s) return;  // merge_record's candidate, then its row_put
+  if (!L.ntl && L.spec) note_wrote(L.d->halt, L.k);
   if (L.ntl < TL) L.tl[L.ntl] = s;
   if (L.ntl <= TL) L.ntl++;
   L.tlast = s;
@@ -141,6 +161,7 @@ __device__ __forceinline__ void cow(ML& L) {
     L.pend = NEVER;
     return;
   }
+  if (L.spec) note_wrote(d.halt, L.k);  // snapshot payloads: the lister's verdict on them is no constant (spec.h)
   for (uint32_t i = L.pend; i != NEVER; i = d.msgs[b][i].pad) d.msgs[b][i].payload = r;
   L.pend = NEVER;
   if (L.ncreq == d.creq_cap) {  // rare: many send-then-write rounds in one tick
@@ -252,7 +273,10 @@ __device__ __forceinline__ bool send_sync(ML& L, uint32_t kind, uint32_t dst, ui
   q->due = L.k + d.lat + (uint32_t)e;
   q->tln = L.ntl;
   L.pend = i;
-  if (e > 0) return true;  // not linked to the receiver's inbound list before its delivery tick
+  if (e > 0) {  // not linked to the receiver's inbound list before its delivery tick
+    if (L.spec) note_wrote(d.halt, L.k);
+    return true;
+  }
   // the receiver's inbound list for the next tick (sharded handles build it when the exchange commits the list);
   // a receiver with several payloads gets them pinned (pin_msg)
   if (d.W == 1) {

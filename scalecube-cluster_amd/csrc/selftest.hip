@@ -638,7 +638,7 @@ int prim_sync_diff(const uint32_t* P, size_t np, const uint32_t* in, size_t inb,
   bf.back(o + 1, d.err, 4);
   bf.back(o + 2, d.ndl, 4);
   bf.back(o + 3, d.ndlw, 4);
-  bf.back(o + 4, d.halt, 4 * HALT_WORDS);
+  bf.back(o + 4, d.halt, 4 * (HALT_LISTED + 1));  // (the words the lister and the diff write)
   bf.back(o + 7, d.hflag + HF_STREAMED, 4);
   return bf.rc;
 }

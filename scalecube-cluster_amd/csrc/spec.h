@@ -2,15 +2,18 @@
 // and the SWIM_EXP bits: everything a kernel or a host path must agree on to take part in a batch (step.hip).
 //
 // A speculative batch is a run of ticks queued with no host wait (one GPU: spec_batch; row shards over RCCL:
-// shard_spec_batch). Three device words, Dev::halt, decide which of the queued launches still do anything. A launch of
-// tick k reads them at its start (volatile loads; hg = halt[HALT_GOSSIP], hd = halt[HALT_DIFF]) and returns at once by
-// the rule of its kernel; nothing waits on the device, and the host reads the words back after the batch.
+// shard_spec_batch). Device words, Dev::halt, decide which of the queued launches still do anything. A launch of
+// tick k reads them at its start (volatile loads; hg = halt[HALT_GOSSIP], hd = halt[HALT_DIFF], hw = halt[HALT_WROTE])
+// and returns at once by the rule of its kernel; nothing waits on the device, and the host reads the words back after
+// the batch. hw takes part only in the launches of a lister-free batch (LS_LF, MT_LF; below): the other one-GPU
+// batches write it (the host looks at it before it enters the mode) but never read it on the device.
 //
 //   kernel (launch of tick k)         predicate             returns at once when
-//   k_ack_resolve (the lister)        halted_lister         hg != 0, or hd != 0 && hd != k + 1
-//   k_sync_diff                       halted_diff           hg != 0 or hd != 0
-//   k_member_tick_t                   halted_member         hg != 0 && hg <= k, or hd != 0
-//   k_sync_redeliver<false>           halted_member         (the same)
+//   k_ack_resolve (the lister)        halted_lister         hg != 0, or hd != 0 && hd != k + 1; LS_LF: or hw != 0 && hw <= k
+//   k_sync_diff                       halted_diff           hg != 0 or hd != 0; LS_LF: or hw != 0 (the same thing: it is
+//                                                           queued before member(k), so any hw it reads is <= k)
+//   k_member_tick_t                   halted_member         hg != 0 && hg <= k, or hd != 0; MT_LF: or hw != 0 && hw <= k
+//   k_sync_redeliver<false>           halted_member         (the same, without the MT_LF clause: no delay in that mode)
 //   k_sync_defer<false>               halted_member         (the same)
 //   k_sync_redeliver<true>            halted_before         hg != 0 && hg <= k
 //   k_sync_defer<true>                halted_uncommitted    hg != 0 && hg <= k + 1
@@ -33,8 +36,19 @@
 //   not committed (the host's path stores that tick's delayed messages); k_pack_all, k_unpack_a and k_inline_in carry
 //   no tick of their own and stop on any halt (the kernels after the gate: on this tick's, too).
 //
+// * a lister-free batch (one GPU, step.hip spec_batch) queues no lister on its untimed ticks: in a
+//   cluster whose rows all equal the baseline and whose write logs are empty the lister's verdict is a constant
+//   (ncand = 0 for every message), and the receivers count the messages as it would have (MT_NOLIST: P1 and the
+//   triage's dead branch). A member kernel that does anything that verdict depends on (note_wrote: a key change or a
+//   merged candidate, a copy-on-write snapshot, a delayed send, a redelivery) stores hw = its tick + 1. member(kw) itself
+//   is complete and right (its own lister, had it run, ran before it); lister(kw + 1) would not be a constant any more,
+//   so every launch of a later tick returns at once, member(k) before its resets, and the host goes on from
+//   lister(kw + 1) with the mode off. A member that writes usually takes a gossip slot in the same launch: then
+//   hg == hw and the gossip halt's path is taken (the host queues the front of kw + 1 again after the gossip plane).
+//
 // The raises: raise_gossip_halt (a member taking a slot, tick_reset), raise_gate_halt (k_unpack_a's gate),
-// raise_diff_halt and count_listed (the lister). The host clears a word after it has acted on it.
+// raise_diff_halt and count_listed (the lister), note_wrote (member control). The host clears a word after it has
+// acted on it.
 #pragma once
 #include <stdint.h>
 
@@ -51,24 +65,36 @@ enum HaltWord : uint32_t {
   HALT_DIFF = 1,
   // entries the lister has listed since create (the host's re-enable rule)
   HALT_LISTED = 2,
-  HALT_WORDS = 3  // adjacent: one copy reads them back
+  // tick + 1 of the latest member-kernel launch of a one-GPU speculative batch that did something the lister's verdict
+  // depends on (note_wrote); the host clears it when it reads it non-zero. Stops the launches of a lister-free batch only.
+  HALT_WROTE = 3,
+  // k_masks_any (the host's look before it enters the lister-free mode): some row has a dirty chunk
+  HALT_MASKS = 4,
+  HALT_WORDS = 5  // adjacent: one copy reads them back
 };
 
 __device__ __forceinline__ bool halted(const uint32_t* halt) { return *(volatile const uint32_t*)halt != 0u; }
-__device__ __forceinline__ bool halted_diff(const uint32_t* halt) {
-  return (*(volatile const uint32_t*)(halt + HALT_GOSSIP) | *(volatile const uint32_t*)(halt + HALT_DIFF)) != 0u;
+// lf: a launch of a lister-free batch (LS_LF, MT_LF): a member kernel of an earlier tick wrote
+__device__ __forceinline__ bool halted_wrote(const uint32_t* halt, uint32_t k, bool lf) {
+  if (!lf) return false;
+  const uint32_t hw = *(volatile const uint32_t*)(halt + HALT_WROTE);
+  return hw != 0u && hw <= k;
 }
-__device__ __forceinline__ bool halted_lister(const uint32_t* halt, uint32_t k) {
+__device__ __forceinline__ bool halted_diff(const uint32_t* halt, bool lf) {
+  return (*(volatile const uint32_t*)(halt + HALT_GOSSIP) | *(volatile const uint32_t*)(halt + HALT_DIFF)) != 0u ||
+         (lf && *(volatile const uint32_t*)(halt + HALT_WROTE) != 0u);
+}
+__device__ __forceinline__ bool halted_lister(const uint32_t* halt, uint32_t k, bool lf) {
   const uint32_t hg = *(volatile const uint32_t*)(halt + HALT_GOSSIP), hd = *(volatile const uint32_t*)(halt + HALT_DIFF);
-  return hg || (hd && hd != k + 1u);
+  return hg || (hd && hd != k + 1u) || halted_wrote(halt, k, lf);
 }
 __device__ __forceinline__ bool halted_before(const uint32_t* halt, uint32_t k) {
   const uint32_t hg = *(volatile const uint32_t*)(halt + HALT_GOSSIP);
   return hg != 0u && hg - 1u < k;
 }
 __device__ __forceinline__ bool halted_uncommitted(const uint32_t* halt, uint32_t k) { return halted_before(halt, k + 1u); }
-__device__ __forceinline__ bool halted_member(const uint32_t* halt, uint32_t k) {
-  return halted_before(halt, k) || *(volatile const uint32_t*)(halt + HALT_DIFF) != 0u;
+__device__ __forceinline__ bool halted_member(const uint32_t* halt, uint32_t k, bool lf = false) {
+  return halted_before(halt, k) || *(volatile const uint32_t*)(halt + HALT_DIFF) != 0u || halted_wrote(halt, k, lf);
 }
 
 __device__ __forceinline__ void raise_gossip_halt(uint32_t* halt, uint32_t k) {
@@ -80,14 +106,23 @@ __device__ __forceinline__ void raise_diff_halt(uint32_t* halt, uint32_t k) {
   *(volatile uint32_t*)(halt + HALT_DIFF) = k + 1u;
 }
 __device__ __forceinline__ void count_listed(uint32_t* halt, uint32_t n) { atomicAdd(halt + HALT_LISTED, n); }
+// member control of tick k did something the lister's verdict depends on (a plain store of the launch's own tick, as
+// raise_gossip_halt: every writer of one launch stores the same value, later launches read it)
+__device__ __forceinline__ void note_wrote(uint32_t* halt, uint32_t k) { *(volatile uint32_t*)(halt + HALT_WROTE) = k + 1u; }
 
 // ---- launch flags ----
 // k_member_tick_t's flag
 enum : uint32_t {
   MT_END = 1u,   // one GPU: the launch does the end-of-tick work (the last block: tick_flag)
   MT_SPEC = 2u,  // a launch of a speculative batch
+  MT_LF = 4u,    // ... of a lister-free one: it returns at once when an earlier tick's member kernel wrote (HALT_WROTE)
+  // no lister ran for this tick (an untimed tick of a lister-free batch): the receivers count their inbound messages
+  // as the lister would have in a clean cluster (P1, the triage's dead branch)
+  MT_NOLIST = 8u,
 };
 constexpr bool mt_spec(uint32_t flag) { return (flag & MT_SPEC) != 0u; }
+constexpr bool mt_lf(uint32_t flag) { return (flag & MT_LF) != 0u; }
+constexpr bool mt_nolist(uint32_t flag) { return (flag & MT_NOLIST) != 0u; }
 // a one-GPU speculative launch: the resets at its start (tick_reset), the member taking a slot raises the halt
 constexpr bool mt_spec_one_gpu(uint32_t flag) { return (flag & (MT_END | MT_SPEC)) == (MT_END | MT_SPEC); }
 // the last block to finish closes the tick (tick_flag): one GPU, not speculative
@@ -97,6 +132,7 @@ constexpr bool mt_closes_tick(uint32_t flag) { return (flag & (MT_END | MT_SPEC)
 enum : uint32_t {
   LS_SPEC = 1u,    // a launch of a speculative batch
   LS_NODIFF = 2u,  // no k_sync_diff follows this launch: a block that lists an entry raises the diff-halt of its tick
+  LS_LF = 4u,      // a (timed) launch of a lister-free batch: the lister and the diff also stop on HALT_WROTE
 };
 
 // ---- the host-mapped flag block (Dev::hflag, swim_handle::hflag) ----
@@ -117,7 +153,7 @@ enum HFlag : uint32_t {
 };
 constexpr uint32_t HF_NPEAK = 5, HF_BYTES = 64;
 static_assert(HF_NHIST + 1 == HF_PEAK0 + HF_NPEAK && HF_NHIST < HF_STREAMED, "the peak words are adjacent");
-static_assert(HALT_GOSSIP == 0 && HALT_DIFF == 1 && HALT_LISTED == 2 && HALT_WORDS == 3,
+static_assert(HALT_GOSSIP == 0 && HALT_DIFF == 1 && HALT_LISTED == 2 && HALT_WROTE == 3 && HALT_MASKS == 4 && HALT_WORDS == 5,
               "the halt words are adjacent: one copy reads them back, word w into hflag[HF_HALT + w]");
 static_assert(HF_WORDS * 4 <= HF_BYTES, "the flag block fits its allocation");
 // Dev::hsh, the device copy of what tick_flag publishes (it writes host memory only on a change): the slots in use, then

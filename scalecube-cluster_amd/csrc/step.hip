@@ -40,6 +40,7 @@ int upload_user_gossips(swim_handle* h, uint32_t k) {
   }
   HIPCK(hipMemcpyAsync(h->ug_dev, h->ugq.data(), h->ugq.size() * 8, hipMemcpyHostToDevice, h->stream));
   launch_user_gossips(d, k, h->ug_dev, (uint32_t)pairs, h->stream);
+  lf_off(h);
   HIPCK(hipStreamSynchronize(h->stream));  // the host queue is reused after this
   h->ugq.clear();
   return SWIM_OK;
@@ -55,14 +56,21 @@ int upload_user_gossips(swim_handle* h, uint32_t k) {
 // member(kd) before its resets, and the host queues diff(kd) over the lists as they stand and goes on from member(kd),
 // without elision until a whole batch has listed nothing (HALT_LISTED, read with the halt words): a cluster with dirty
 // rows pays one extra host wait per dirty spell, not one per tick. Timed ticks keep their event-carrying diff launch.
+// While the handle is lister-free as well (lf_on), an untimed tick has no front at all: member(k) runs
+// straight after member(k - 1), flagged MT_NOLIST, and counts its messages in the lister's place. A member kernel that
+// writes stores HALT_WROTE = its tick kw + 1: every launch of a later tick returns at once, and the host goes on from
+// lister(kw + 1) with both modes off. Only the launches of speculative batches store the word (a tick run on its own,
+// tick_one_gpu, leaves the mode instead), and the host clears it after every batch that set it.
 int spec_batch(swim_handle* h, Step& s) {
   const Dev& d = h->d;
   const uint32_t k = (uint32_t)h->tick, i = s.i, nb = s.nb;
   const bool can = diff_elidable(d) && !h->no_elide, elide = can && h->elide_on;
+  const bool lf = elide && h->lf_on;
   const uint32_t k0 = s.need_front ? k : k + 1u;  // the first tick whose front this batch queues
   auto front = [&](uint32_t kk, uint32_t jj) {
     const TickEvents* te = events_of(h, kk, jj);
-    launch_diff(d, kk, h->stream, te, LS_SPEC | (elide && !te ? LS_NODIFF : 0u));
+    if (lf && !te) return;
+    launch_diff(d, kk, h->stream, te, LS_SPEC | (lf ? LS_LF : 0u) | (elide && !te ? LS_NODIFF : 0u));
   };
   // the ticks of [from, to) that ran without a diff launch
   auto elided = [&](uint32_t from, uint32_t to) {
@@ -70,26 +78,56 @@ int spec_batch(swim_handle* h, Step& s) {
     for (uint32_t t = std::max(from, 1u); elide && t < to; ++t) c += !prof_timed(h, t);
     return c;
   };
+  auto listerless = [&](uint32_t from, uint32_t to) { return lf ? elided(from, to) : 0ull; };  // ... without a lister
   for (uint32_t j = i; j < nb; ++j) {
     const uint32_t kj = k + (j - i);
+    const TickEvents* te = events_of(h, kj, j);
     if (s.need_front) front(kj, j);
-    launch_member(d, kj, h->stream, events_of(h, kj, j), true);
+    // (the first tick's front may have been queued with the tick before it: then its lister ran)
+    const uint32_t mlf = !lf ? 0u : MT_LF | (kj >= k0 && !te ? MT_NOLIST : 0u);
+    launch_member(d, kj, h->stream, te, true, false, mlf);
     s.need_front = j + 1 == nb;
     if (!s.need_front) front(kj + 1, j + 1);
   }
   HIPCK(hipMemcpyAsync((void*)(h->hflag + HF_HALT), d.halt, HALT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
   const volatile uint32_t* hw = h->hflag + HF_HALT;
-  const uint32_t hk = hw[HALT_GOSSIP], hd = hw[HALT_DIFF], listed = hw[HALT_LISTED];
+  const uint32_t hk = hw[HALT_GOSSIP], hd = hw[HALT_DIFF], listed = hw[HALT_LISTED], hwr = hw[HALT_WROTE];
   const bool quiet = listed == h->listed_seen;
   h->listed_seen = listed;
+  if (hwr != 0) HIPCK(hipMemsetAsync(&d.halt[HALT_WROTE], 0, 4, h->stream));
   if (hk != 0 && hd != 0) return fail(h, SWIM_EDEVICE, "speculative batch: a gossip halt and a diff-halt");
+  if (lf && hd != 0) return fail(h, SWIM_EDEVICE, "lister-free batch: a diff-halt");
+  if (lf && hwr != 0 && hk == 0) {  // member(kw) wrote: it is complete, nothing of a later tick ran
+    h->lf_on = h->elide_on = false;
+    const uint32_t kw = hwr - 1u;
+    if (kw < k || kw >= k + (nb - i)) return fail(h, SWIM_EDEVICE, "lister-free batch: bad wrote tick");
+    h->diff_elided += elided(k0, kw + 1u);
+    h->lf_ticks += listerless(k0, kw + 1u);
+    h->lf_stops++;
+    h->gossip_ran = false;
+    h->tick = kw + 1ull;
+    s.i = i + (kw + 1u - k);
+    s.need_front = true;  // from lister(kw + 1)
+    return SWIM_OK;
+  }
   if (hk == 0 && hd == 0) {  // the whole batch ran
     h->diff_elided += elided(k0, k + (nb - i));
+    h->lf_ticks += listerless(k0, k + (nb - i));
     h->elide_on = quiet;
     h->tick += nb - i;
     s.i = nb;
     h->gossip_ran = false;
+    if (lf) {
+      h->lf_on = quiet;
+    } else if (elide && quiet && hwr == 0 && nb - i >= 2 && !h->no_lf && !d.dly_on) {
+      // an elided batch of two ticks or more that listed nothing and wrote nothing: both write logs the next lister
+      // would read are empty. Lister-free from the next batch on if every row is clean as well (one pass, only here)
+      launch_masks_any(d, h->stream);
+      HIPCK(hipMemcpyAsync((void*)(h->hflag + HF_HALT + HALT_MASKS), &d.halt[HALT_MASKS], 4, hipMemcpyDeviceToHost, h->stream));
+      HIPCK(hipStreamSynchronize(h->stream));
+      h->lf_on = hw[HALT_MASKS] == 0;
+    }
     return SWIM_OK;
   }
   if (hd != 0) {  // lister(kd) listed work and no diff was queued: ticks before kd are complete, member(kd) has not run
@@ -100,7 +138,7 @@ int spec_batch(swim_handle* h, Step& s) {
     launch_diff_listed(d, kd, h->stream);
     h->diff_elided += elided(k0, kd);
     h->diff_halts++;
-    h->elide_on = false;
+    h->elide_on = h->lf_on = false;
     if (kd > k) h->gossip_ran = false;
     h->tick = kd;
     s.i = i + (kd - k);
@@ -129,7 +167,9 @@ int spec_batch(swim_handle* h, Step& s) {
   h->gossip_ran = true;
   s.need_front = true;  // the front of kh + 1 returned at once
   h->diff_elided += elided(k0, kh + 1u);
-  h->elide_on = false;   // gossips change rows: the next batch queues its diffs and looks at what the lister lists
+  h->lf_ticks += listerless(k0, kh + 1u);
+  // gossips change rows: the next batch queues its listers and diffs and looks at what the lister lists
+  h->elide_on = h->lf_on = false;
   h->tick = kh + 1ull;
   s.i = ih + 1;
   return SWIM_OK;
@@ -140,6 +180,7 @@ int tick_one_gpu(swim_handle* h, Step& s) {
   const Dev& d = h->d;
   const uint32_t k = (uint32_t)h->tick, i = s.i;
   const TickEvents* te = events_of(h, h->tick, i);
+  lf_off(h);  // (this member launch does not say whether it wrote: HALT_WROTE is a speculative batch's word)
   // SYNC diff(k) was queued in the previous iteration, except for the first tick of this call
   if (s.need_front) launch_diff(d, k, h->stream, te);
   launch_member(d, k, h->stream, te, false, h->gossip_ran && !d.fastp4);
@@ -158,6 +199,7 @@ int tick_one_gpu(swim_handle* h, Step& s) {
   if (nosync) {
   } else if (h->hflag[HF_USED] != 0 || h->no_skip) {
     launch_gossip(d, k, h->stream, te);
+    lf_off(h);
     int sr;
     if (h->stats && (sr = stats_dump(h, k)) != SWIM_OK) return sr;
   } else if (te && te->all) {
@@ -255,6 +297,7 @@ static int rebase_check(swim_handle* h) {
     const unsigned long long st = c[3ull * q], df = c[3ull * q + 1], r = c[3ull * q + 2];
     if (st < df + thr || r >= d.NL) continue;
     launch_rebase(d, q, (uint32_t)r, h->stream);
+    lf_off(h);  // (the masks change)
     h->rebases++;
   }
   return SWIM_OK;

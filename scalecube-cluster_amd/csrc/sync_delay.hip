@@ -45,6 +45,7 @@ __global__ void __launch_bounds__(256) k_sync_redeliver(Dev d, uint32_t k, uint3
         m.ncand = 0;
         m.pad = NEVER;
         m.pin = NEVER;
+        if (!SHARDED && spec) note_wrote(d.halt, k);  // a snapshot payload in the next tick's lists (spec.h)
         if constexpr (SHARDED) {  // the inbound list of the next tick while it is assembled
           d.mtmp[i] = m;
         } else {

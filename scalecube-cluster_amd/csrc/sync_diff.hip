@@ -341,7 +341,7 @@ constexpr uint32_t DIFF_WAVES = 7;
 template <bool SHARDED>
 __global__ void __launch_bounds__(256, DIFF_WAVES) k_sync_diff(const Dev* __restrict__ dp, uint32_t b, uint32_t timed, uint32_t spec) {
   const Dev& d = *dp;  // global, not kernarg (as k_member_tick): a by-value Dev of this size was copied to scratch
-  if (spec && halted_diff(d.halt)) return;  // a speculative batch halted at an earlier tick (spec.h)
+  if (spec && halted_diff(d.halt, (spec & LS_LF) != 0u)) return;  // a speculative batch halted at an earlier tick (spec.h)
   __shared__ uint32_t scan[256];
   __shared__ uint32_t base;
   // (timed launches are bracketed by HIP events on the stream. A self-timing variant, first block start to last block
@@ -542,7 +542,7 @@ __device__ __forceinline__ bool res_wave(const ResArgs& d, uint32_t i, uint32_t 
 // which every later launch of the batch returns at once and the host runs diff(k) itself. The blocks of this launch go
 // on whatever their own tick's diff-halt says (halted_lister: the list must be complete); nothing waits on the device.
 __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint32_t spec, uint32_t timed) {
-  if (spec && halted_lister(d.halt, k)) return;
+  if (spec && halted_lister(d.halt, k, (spec & LS_LF) != 0u)) return;
   __shared__ uint32_t sv_[8][64], sc_[8][64];
   __shared__ uint4 wlist[8];
   // per block and round: narrow list entries, wide ones, resolved messages, narrow messages (listed or decided here),
@@ -714,6 +714,20 @@ void launch_rebase(const Dev& d, uint32_t c, uint32_t r, void* stream) {
   hipLaunchKernelGGL(k_rebase, dim3(min(d.NL, 4096u)), dim3(256), 0, (hipStream_t)stream, d, c, r);
 }
 
+// one GPU, between batches (step.hip, before the lister-free mode is entered): is any chunk of any row dirty? One pass
+// over the members' records; a wave that finds a set bit stores HALT_MASKS (the host cleared it).
+__global__ void __launch_bounds__(256) k_masks_any(Dev d) {
+  const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t any = 0;
+  if (li < d.NL)
+    for (uint32_t w = 0; w < d.MW; ++w) any |= d.ms[li].dirty[w];
+  if (__ballot(any != 0ull) && (threadIdx.x & 63u) == 0) *(volatile uint32_t*)(d.halt + HALT_MASKS) = 1u;
+}
+void launch_masks_any(const Dev& d, void* stream) {
+  hipMemsetAsync(&d.halt[HALT_MASKS], 0, 4, (hipStream_t)stream);
+  hipLaunchKernelGGL(k_masks_any, dim3((d.NL + 255) / 256), dim3(256), 0, (hipStream_t)stream, d);
+}
+
 // one GPU: the dirty masks' invariant, tested directly: all the rows whose bit c is clear hold the same chunk c (keys,
 // and their 8-bit shadows): the baseline's. k_dirty_ref finds, per chunk, the first such row; k_dirty_check compares
 // every other one with it, one block per (row, chunk), grid-strided, and counts the dirty pairs.
@@ -800,7 +814,7 @@ void launch_diff(const Dev& d, uint32_t k, void* stream, const TickEvents* prof,
   hipStream_t st = (hipStream_t)stream;
   if (!diff_elidable(d)) ls &= ~LS_NODIFF;
   launch_ack_resolve(d, k, st, ls, prof != nullptr);
-  if (k > 0 && !(ls & LS_NODIFF)) launch_sync_diff(d, (k - 1) & 1, st, prof ? 1u : 0u, ls & LS_SPEC, prof, grid);
+  if (k > 0 && !(ls & LS_NODIFF)) launch_sync_diff(d, (k - 1) & 1, st, prof ? 1u : 0u, ls & (LS_SPEC | LS_LF), prof, grid);
 }
 
 void launch_diff_listed(const Dev& d, uint32_t k, void* stream, uint32_t grid) {

@@ -276,7 +276,8 @@ def prim_eval(lib, op, params, inp, out, device=0):
     if rc != 0:
         raise RuntimeError(f"swim_debug_prim_eval(op={op}, params={list(params)}) rc={rc}")
     return out
-DD_NAMES = ["skipped", "streamed", "msg_skipped", "rebases", "dirty_rows", "pin_decided", "diff_elided", "diff_halts"]
+DD_NAMES = ["skipped", "streamed", "msg_skipped", "rebases", "dirty_rows", "pin_decided", "diff_elided", "diff_halts",
+            "lister_free_ticks", "lister_free_stops"]
 CAP_NAMES = ["slots", "ring", "receipts", "replay", "history", "growths"]
 
 
