@@ -178,7 +178,66 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
  *            that is no arena row (or PAY_RX | ri with ri >= nrx), a list entry whose message, rows, place, item or chunk
  *            bits do not exist, a log subject >= N, an m_head / m_next link >= nmsg or a list that does not end, chunk-mask
  *            bits past NCHUNK, an rx_off that is no multiple of 16 or whose popcount(mask) chunks pass the receive buffer,
- *            non-zero padding keys between N and NS, k = 0, flags that do not go together */
+ *            non-zero padding keys between N and NS, k = 0, flags that do not go together
+ *
+ * The row-shard exchange codec (shard.hip), each kernel in the grid the engine launches it in, on a Dev that
+ * holds only what it reads. The in/out buffers are preset by the caller (a sentinel), so a test also sees what was not
+ * written. Capacity overflows (E_XCAP, E_MSGS) are the kernels' own error paths and reach them; everything else the
+ * layouts do not allow is SWIM_EINVAL before any launch. At most 32 params.
+ *
+ * XPACK      k_pack_all at (16, W) on one rank's tick output; NS, NCHUNK, MW follow from N as for SYNC_DIFF.
+ *            params (22): N; W (2..8); rank; R local rows (1..64: members shard_lo(N, W, rank) .. + R - 1, inside the
+ *              shard); b (tick parity); flags (SWIM_PRIM_XP_*); nmsg; MSGCAP (nmsg <= MSGCAP <= 4096); ARENA_ROWS A (<= 64);
+ *              NSCAP, RRCAP (1..1024); RQCAP, CHCAP (<= 2^20); XA_PEER (a multiple of 16, 32 .. 2^26: chunks are stored
+ *              16 B at a time); XI (a multiple of 8, 64 .. 2^20); gossip slots in use (> 0: XFLAG_GOSSIP); xn[0], xn[1] (the
+ *              tick's slot and round record counts, which may pass NSCAP / RRCAP); nsr, nrr (records supplied:
+ *              min(xn[0], NSCAP) <= nsr <= NSCAP, the same for rounds); xn[4] (messages already queued in mtmp); sentinel
+ *              (the value of the xn words the kernel does not use)
+ *            flags: XP_ACKRES the log prefixes are copied; XP_INLINE the inline blocks are written (Dev::inl); XP_SPEC a
+ *              speculative launch, XP_HALTED with it: the halt word is already raised; XP_TLOG the input has the log;
+ *              XP_INLINE_OUT k_inline_out at (W) then writes its blocks of the same regions and count words into xi_out
+ *              (XA_PEER >= XI - 8)
+ *            in  rdirty u64[R][MW]; arena_dirty u64[A][MW]; rowk[R][NS]; arena[A][NS]; msgs[nmsg][13] (whole SyncMsg
+ *                records); XP_TLOG: tlog[R][16] of parity b; ns_rec[nsr][8]; rr_rec[nrr][12]
+ *            out (bytes, all in/out but the last three) xa_send[W][XA_PEER]; xa_scnt u64[W]; xi_send[W][XI]; xi_out[W][XI];
+ *                mtmp[MSGCAP][13]; mlog[MSGCAP][16]; xn[8]; err; halt[0]
+ *            EINVAL: a src outside the R rows, a dst >= N, a payload that is neither 0xFFFFFFFF nor an arena row, mask
+ *            bits past NCHUNK, a KF_RES message with 1 <= tln <= 16 under XP_ACKRES without XP_TLOG, counts or sizes out
+ *            of the ranges above, XP_HALTED without XP_SPEC
+ * PACK_B     k_pack_b at (64, W). params (5): W, rank, DCAP (1..2^20), *xd_n, XB_PEER (a multiple of 8, 16 .. 2^24)
+ *            in  xd u64[min(*xd_n, DCAP)]
+ *            out xb_send[W][XB_PEER] in/out; xb_scnt u64[W] in/out; err; 0
+ * INLINE_IN  k_inline_in at (W). params (4): W, XI, cap (a multiple of 8, XI - 8 .. 2^24: bytes per receive region), flags
+ *              (1: a speculative launch, which reads the halt word; 3: that word is raised)
+ *            in  irecv[W][XI] (count word, then the block); scnt u64[W]
+ *            out recv[W][cap] in/out; rcnt u64[W] in/out; host u64[2 W] in/out
+ * XUNPACK    k_unpack_a at (32, W), with msgs_commit and (XU_END) tick_end, on caller-built receive regions; with
+ *            XU_INLINE_IN k_inline_in at (W) first expands inline blocks into regions preset to the sentinel's low byte.
+ *            params (18): N; W (2..8); rank; k (the tick, < 2^31: the inbound list of buffer k & 1); flags (SWIM_PRIM_XU_*);
+ *              MSGCAP (1..4096); RXCAP (<= 4096); ARENA_ROWS (<= 64); XA_PEER (a multiple of 16, max(32, XI - 8) .. 2^26); XI;
+ *              nloc (local messages already in mtmp: xn[4]); SLOTS (a multiple of 64, 64..4096), BCAP (a power of two <= 64),
+ *              LOGW (1..8), F (1..8), EXPB, gossip_t (>= 1) (all six with XU_GOSSIP only, N <= 65536 then); sentinel
+ *            flags: XU_END the launch closes the tick; XU_SPEC a speculative launch (the gate is evaluated), XU_HALTED with
+ *              it: the halt word is already raised; XU_ACKRES log prefixes are copied; XU_GOSSIP the gossip plane's arrays
+ *              exist (without it no region may hold a slot or round record)
+ *            in  regions [W][XA_PEER], or with XU_INLINE_IN blocks [W][XI] (count word first); rcnt u64[W] (ignored with
+ *                XU_INLINE_IN); scnt u64[W] (this rank's sent count words); mtmp[nloc][13]; XU_GOSSIP: firstGossip[N],
+ *                rhead[N], rtail[N], log_pos[N], log_spread[N][LOGW]
+ *            out (bytes; in/out unless said) msgs[MSGCAP][13] of buffer k & 1; m_head[N] of that buffer (starts empty: every
+ *                word 0xFFFFFFFF); m_next[MSGCAP]; rx_mask u64[RXCAP][MW]; rx_off u64[RXCAP]; mlog[MSGCAP][16]; u32[18] =
+ *                nmsg[2], arena_used[2], xn[8], err, halt[0], pool_used, rc_n, ndl, ndlw (start: nmsg, the other buffer's
+ *                arena_used, xn[0..3], xn[7] and the last four at the sentinel; this buffer's arena_used, xn[5], xn[6], err 0;
+ *                xn[4] = nloc); xa_scnt u64[W] (starts as scnt); xb_scnt u64[W]; xdone[2 W]; xa_rcnt u64[W]; host u64[2 W];
+ *                XU_GOSSIP: slot_gid u64[SLOTS]; slot_key u64[SLOTS]; slot_subj, slot_ctick, slot_exp, slot_used [SLOTS] each;
+ *                GU, DM u64[SLOTS / 64] each (start 0); S u16[N][SLOTS]; HB u64[N][SLOTS / 64] (starts 0); rg[N][BCAP];
+ *                [8][N] = rtail (starts as given), held (starts 0), tround, tcnt, tspread, tperiod, spchg, log_pos (starts as
+ *                given); T[N][F]; [3][N][LOGW] = log_tick, log_spread (starts as given), log_cnt; log_tg[N][LOGW][F]
+ *            EINVAL: unless a speculative launch is certain to stop at its halt word or gate, every region of a peer with a
+ *            count >= 32 is checked against its byte count and XA_PEER: records, entries and data_off (a multiple of 16)
+ *            inside it, base + popcount(mask) <= nchunk chunks inside it, mask bits past NCHUNK, src / dst / origins / round
+ *            members / targets < N, slot ids < SLOTS, cnt <= F; an inline block whose region is longer than it (the engine
+ *            fetches the rest first) unless the gate stops the launch; an mtmp entry with src or dst >= N; rtail - rhead >
+ *            BCAP; sizes out of the ranges above */
 #define SWIM_PRIM_SCAN 0u
 #define SWIM_PRIM_SEG_SORT 1u
 #define SWIM_PRIM_ROUTING 2u
@@ -188,6 +247,22 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
 #define SWIM_PRIM_FEISTEL 6u
 #define SWIM_PRIM_RING_MOVE 7u
 #define SWIM_PRIM_SYNC_DIFF 8u
+#define SWIM_PRIM_XPACK 9u
+#define SWIM_PRIM_PACK_B 10u
+#define SWIM_PRIM_INLINE_IN 11u
+#define SWIM_PRIM_XUNPACK 12u
+#define SWIM_PRIM_XP_ACKRES 1u
+#define SWIM_PRIM_XP_INLINE 2u
+#define SWIM_PRIM_XP_SPEC 4u
+#define SWIM_PRIM_XP_HALTED 8u
+#define SWIM_PRIM_XP_TLOG 16u
+#define SWIM_PRIM_XP_INLINE_OUT 32u
+#define SWIM_PRIM_XU_END 1u
+#define SWIM_PRIM_XU_SPEC 2u
+#define SWIM_PRIM_XU_HALTED 4u
+#define SWIM_PRIM_XU_ACKRES 8u
+#define SWIM_PRIM_XU_INLINE_IN 16u
+#define SWIM_PRIM_XU_GOSSIP 32u
 #define SWIM_PRIM_SD_K8 1u
 #define SWIM_PRIM_SD_LISTER 2u
 #define SWIM_PRIM_SD_LISTS 4u

@@ -1,7 +1,7 @@
 // selftest.hip — swim_selftest_eval (include/swimhip_selftest.h): the device primitives the simulation kernels call,
 // evaluated on caller inputs in a gfx950 kernel, so the reference's known answers pin the device code itself; and
 // swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives and the SYNC diff with its
-// lister the same way (engine only).
+// lister the same way, and the row-shard exchange codec (shard.hip) in the engine's own grids (engine only).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -81,6 +81,14 @@ namespace swim {
 __global__ void __launch_bounds__(256) k_seg_sort(uint64_t* key, uint32_t* val, uint64_t* tkey, uint32_t* tval,
                                                   const uint32_t* off, const uint32_t* cnt, const uint32_t* sg,
                                                   const uint32_t* nsg, uint32_t run, unsigned long long* fb);  // route.hip
+__global__ void __launch_bounds__(256) k_pack_all(Dev d, uint32_t b, uint32_t spec);                         // shard.hip
+__global__ void __launch_bounds__(256) k_pack_b(Dev d);
+__global__ void __launch_bounds__(256) k_inline_out(const uint8_t* send, uint64_t cap, const unsigned long long* scnt,
+                                                    uint8_t* isend, uint32_t XI);
+__global__ void __launch_bounds__(256) k_inline_in(const uint8_t* irecv, uint8_t* recv, uint64_t cap,
+                                                   const unsigned long long* scnt, unsigned long long* rcnt,
+                                                   unsigned long long* host, uint32_t W, const uint32_t* halt, uint32_t XI);
+__global__ void __launch_bounds__(256) k_unpack_a(Dev d, uint32_t k, uint32_t end, uint32_t spec);
 
 // a, r: [3][T] words per thread, T = gridDim.x * 256
 __global__ void __launch_bounds__(256) k_prim_wave(uint32_t sub, const uint32_t* a, uint32_t* r, uint32_t* ctr, uint32_t T) {
@@ -643,13 +651,394 @@ int prim_sync_diff(const uint32_t* P, size_t np, const uint32_t* in, size_t inb,
   return bf.rc;
 }
 
+// ---- the row-shard exchange codec (shard.hip) on a Dev that holds only what its kernels read, in the engine's grids.
+// Layouts: include/swimhip_debug.h. The kernels trust their inputs (a peer is the same program), so everything the
+// layouts do not allow is refused here; a capacity overflow is no such thing and reaches the kernel.
+constexpr uint32_t SMW = sizeof(SyncMsg) / 4;  // a whole record, as words
+
+int prim_xpack(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 22) return SWIM_EINVAL;
+  const uint32_t N = P[0], W = P[1], rank = P[2], R = P[3], b = P[4], fl = P[5], nmsg = P[6], MSGCAP = P[7], AR = P[8],
+                 NSCAP = P[9], RRCAP = P[10], RQCAP = P[11], CHCAP = P[12], XA = P[13], XI = P[14], used = P[15], xn0 = P[16],
+                 xn1 = P[17], nsr = P[18], nrr = P[19], xn4 = P[20], sent = P[21];
+  const bool ackres = fl & SWIM_PRIM_XP_ACKRES, inl = fl & SWIM_PRIM_XP_INLINE, spec = fl & SWIM_PRIM_XP_SPEC,
+             halt = fl & SWIM_PRIM_XP_HALTED, has_log = fl & SWIM_PRIM_XP_TLOG, iout = fl & SWIM_PRIM_XP_INLINE_OUT;
+  if (W < 2 || W > 8 || rank >= W || N < W || N > MSW * 64 * CH || R < 1 || R > 64 || b > 1 || fl > 63 || MSGCAP < 1 ||
+      MSGCAP > 4096 || nmsg > MSGCAP || AR > 64 || NSCAP < 1 || NSCAP > 1024 || RRCAP < 1 || RRCAP > 1024 || RQCAP > (1u << 20) ||
+      CHCAP > (1u << 20) || (XA & 15u) || XA < 32 || XA > (1u << 26) || (XI & 7u) || XI < 64 || XI > (1u << 20) ||
+      used > (1u << 20) || xn4 > (1u << 20) || nsr > NSCAP || nrr > RRCAP || std::min(xn0, NSCAP) > nsr ||
+      std::min(xn1, RRCAP) > nrr || (halt && !spec) || (iout && (uint64_t)XA + 8 < XI))
+    return SWIM_EINVAL;
+  const uint32_t lo = shard_lo(N, W, rank), hi = shard_lo(N, W, rank + 1);
+  if ((uint64_t)lo + R > hi) return SWIM_EINVAL;
+  const KeyPlaneSizes z = key_plane_sizes(N);
+  const uint32_t NS = z.NS, NCHUNK = z.NCHUNK, MW = z.MW;
+  const uint64_t w_rd = 2ull * R * MW, w_ad = 2ull * AR * MW, w_rows = (uint64_t)R * NS, w_arena = (uint64_t)AR * NS,
+                 w_msgs = (uint64_t)SMW * nmsg, w_log = has_log ? (uint64_t)R * TL : 0, w_ns = (uint64_t)NSW * nsr,
+                 w_rr = (uint64_t)RRW * nrr;
+  if (inb != 4 * (w_rd + w_ad + w_rows + w_arena + w_msgs + w_log + w_ns + w_rr)) return SWIM_EINVAL;
+  const uint64_t b_xa = (uint64_t)W * XA, b_xi = (uint64_t)W * XI, w_mtmp = (uint64_t)SMW * MSGCAP, w_mlog = (uint64_t)TL * MSGCAP;
+  if (outb != b_xa + 8ull * W + 2 * b_xi + 4 * (w_mtmp + w_mlog + 10)) return SWIM_EINVAL;
+  const uint64_t *i_rd = (const uint64_t*)in, *i_ad = i_rd + (size_t)R * MW;
+  const uint32_t *i_rows = in + w_rd + w_ad, *i_arena = i_rows + w_rows, *i_msgs = i_arena + w_arena, *i_log = i_msgs + w_msgs,
+                 *i_ns = i_log + w_log, *i_rr = i_ns + w_ns;
+  for (uint32_t r = 0; r < R + AR; ++r)  // mask bits past NCHUNK
+    for (uint32_t q = 0; q < MW; ++q) {
+      const uint32_t top = NCHUNK - 64 * q >= 64 ? 64 : NCHUNK - 64 * q;
+      if (top < 64 && (i_rd[(size_t)r * MW + q] >> top)) return SWIM_EINVAL;
+    }
+  for (uint32_t i = 0; i < nmsg; ++i) {
+    SyncMsg mm;
+    memcpy(&mm, i_msgs + (size_t)SMW * i, sizeof mm);
+    if (mm.src < lo || mm.src - lo >= R || mm.dst >= N || (mm.payload != NEVER && mm.payload >= AR)) return SWIM_EINVAL;
+    if (ackres && (mm.kind & KF_RES) && mm.tln >= 1 && mm.tln <= TL && !has_log) return SWIM_EINVAL;
+  }
+  uint8_t* o8 = (uint8_t*)out;
+  uint8_t *o_xa = o8, *o_scnt = o_xa + b_xa, *o_xi = o_scnt + 8ull * W, *o_xo = o_xi + b_xi, *o_mtmp = o_xo + b_xi,
+          *o_mlog = o_mtmp + 4 * w_mtmp, *o_xn = o_mlog + 4 * w_mlog;
+
+  PrimBufs bf;
+  Dev d;  // only the fields k_pack_all reads
+  memset(&d, 0, sizeof d);
+  d.N = N, d.NS = NS, d.NCHUNK = NCHUNK, d.MW = MW, d.W = W, d.rank = rank, d.lo = lo, d.hi = hi, d.NL = R;
+  d.MSGCAP = MSGCAP, d.ARENA_ROWS = AR, d.NSCAP = NSCAP, d.RRCAP = RRCAP, d.RQCAP = RQCAP, d.CHCAP = CHCAP, d.XA_PEER = XA;
+  d.XI = XI, d.inl = inl ? 1u : 0u, d.ackres = ackres ? ACKRES_ON : 0u, d.SPR = used;
+  d.rdirty = bf.get<uint64_t>((size_t)R * MW, i_rd, (size_t)R * MW);
+  d.arena_dirty[b] = bf.get<uint64_t>((size_t)AR * MW, i_ad, (size_t)AR * MW);
+  d.rowk = bf.get<uint32_t>(w_rows, i_rows, w_rows);
+  d.arena[b] = bf.get<uint32_t>(w_arena, i_arena, w_arena);
+  d.msgs[b] = (SyncMsg*)bf.get<uint32_t>((uint64_t)SMW * MSGCAP, i_msgs, w_msgs);
+  uint32_t nm[2] = {0, 0};
+  nm[b] = nmsg;
+  d.nmsg = bf.get<uint32_t>(2, nm, 2);
+  d.tlog = bf.get<uint32_t>(2ull * R * TL);
+  if (bf.rc == SWIM_OK && has_log && hipMemcpy(d.tlog + (size_t)b * R * TL, i_log, 4 * w_log, hipMemcpyHostToDevice) != hipSuccess)
+    bf.rc = SWIM_EDEVICE;
+  d.ns_rec = bf.get<uint32_t>((uint64_t)NSW * NSCAP, i_ns, w_ns);
+  d.rr_rec = bf.get<uint32_t>((uint64_t)RRW * RRCAP, i_rr, w_rr);
+  d.free_top = bf.get<int32_t>(1);
+  const uint32_t xn[8] = {xn0, xn1, sent, sent, xn4, sent, sent, sent};
+  d.xn = bf.get<uint32_t>(8, xn, 8);
+  d.xdone = bf.get<uint32_t>(2ull * W);
+  d.err = bf.get<uint32_t>(8);
+  d.ctr_sh = bf.get<unsigned long long>((size_t)CSH * CSTRIDE);
+  d.halt = (uint32_t*)(d.ctr_sh + SH_HALT);
+  const uint32_t h1 = 1;
+  if (bf.rc == SWIM_OK && halt && hipMemcpy(d.halt, &h1, 4, hipMemcpyHostToDevice) != hipSuccess) bf.rc = SWIM_EDEVICE;
+  d.xa_send = bf.get<uint8_t>(b_xa, o_xa, b_xa);
+  d.xa_scnt = bf.get<unsigned long long>(W, o_scnt, W);
+  d.xi_send = bf.get<uint8_t>(b_xi, o_xi, b_xi);
+  uint8_t* xo = bf.get<uint8_t>(b_xi, o_xo, b_xi);
+  d.mtmp = (SyncMsg*)bf.get<uint32_t>(w_mtmp, o_mtmp, w_mtmp);
+  d.mlog = bf.get<uint32_t>(w_mlog, o_mlog, w_mlog);
+  if (bf.rc != SWIM_OK) return bf.rc;
+
+  hipLaunchKernelGGL(k_pack_all, dim3(16, W), dim3(256), 0, 0, d, b, spec ? 1u : 0u);  // launch_tick_a's grid
+  if (iout) hipLaunchKernelGGL(k_inline_out, dim3(W), dim3(256), 0, 0, d.xa_send, (uint64_t)XA, d.xa_scnt, xo, XI);
+  if (!bf.ran()) return bf.rc;
+  bf.back(o_xa, d.xa_send, b_xa);
+  bf.back(o_scnt, d.xa_scnt, 8ull * W);
+  bf.back(o_xi, d.xi_send, b_xi);
+  bf.back(o_xo, xo, b_xi);
+  bf.back(o_mtmp, d.mtmp, 4 * w_mtmp);
+  bf.back(o_mlog, d.mlog, 4 * w_mlog);
+  bf.back(o_xn, d.xn, 32);
+  bf.back(o_xn + 32, d.err, 4);
+  bf.back(o_xn + 36, d.halt, 4);
+  return bf.rc;
+}
+
+int prim_pack_b(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 5) return SWIM_EINVAL;
+  const uint32_t W = P[0], rank = P[1], DCAP = P[2], xd_n = P[3], XB = P[4];
+  const uint64_t nd = std::min(xd_n, DCAP);
+  if (W < 2 || W > 8 || rank >= W || DCAP < 1 || DCAP > (1u << 20) || (XB & 7u) || XB < 16 || XB > (1u << 24) || inb != 8 * nd ||
+      outb != (uint64_t)W * XB + 8ull * W + 8)
+    return SWIM_EINVAL;
+  uint8_t* o8 = (uint8_t*)out;
+  PrimBufs bf;
+  Dev d;  // only the fields k_pack_b reads
+  memset(&d, 0, sizeof d);
+  d.W = W, d.rank = rank, d.DCAP = DCAP, d.XB_PEER = XB;
+  d.xd = bf.get<uint64_t>(DCAP, in, nd);
+  d.xd_n = bf.get<uint32_t>(1, &xd_n, 1);
+  d.err = bf.get<uint32_t>(8);
+  d.xb_send = bf.get<uint8_t>((uint64_t)W * XB, o8, (uint64_t)W * XB);
+  d.xb_scnt = bf.get<unsigned long long>(W, o8 + (uint64_t)W * XB, W);
+  if (bf.rc != SWIM_OK) return bf.rc;
+  hipLaunchKernelGGL(k_pack_b, dim3(64, W), dim3(256), 0, 0, d);  // launch_tick_b's grid
+  if (bf.ran() && bf.back(o8, d.xb_send, (uint64_t)W * XB) && bf.back(o8 + (uint64_t)W * XB, d.xb_scnt, 8ull * W)) {
+    uint32_t e[2] = {0, 0};
+    if (bf.back(e, d.err, 4)) memcpy(o8 + (uint64_t)W * XB + 8ull * W, e, 8);
+  }
+  return bf.rc;
+}
+
+// a walk over a byte buffer in the order a layout lists its parts
+struct Cursor {
+  uint8_t* p;
+  uint8_t* take(uint64_t bytes) {
+    uint8_t* r = p;
+    p += bytes;
+    return r;
+  }
+};
+
+// k_unpack_a (with msgs_commit and tick_end), optionally after k_inline_in, on caller-built receive regions
+int prim_xunpack(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 18) return SWIM_EINVAL;
+  const uint32_t N = P[0], W = P[1], rank = P[2], k = P[3], fl = P[4], MSGCAP = P[5], RXCAP = P[6], AR = P[7], XA = P[8],
+                 XI = P[9], nloc = P[10], SLOTS = P[11], BCAP = P[12], LOGW = P[13], F = P[14], EXPB = P[15], gossip_t = P[16],
+                 sent = P[17];
+  const bool end = fl & SWIM_PRIM_XU_END, spec = fl & SWIM_PRIM_XU_SPEC, halt = fl & SWIM_PRIM_XU_HALTED,
+             ackres = fl & SWIM_PRIM_XU_ACKRES, iin = fl & SWIM_PRIM_XU_INLINE_IN, gossip = fl & SWIM_PRIM_XU_GOSSIP;
+  if (W < 2 || W > 8 || rank >= W || N < W || N > MSW * 64 * CH || k >= (1u << 31) || fl > 63 || (halt && !spec) || MSGCAP < 1 ||
+      MSGCAP > 4096 || RXCAP > 4096 || AR > 64 || (XA & 15u) || XA < 32 || XA > (1u << 26) || (XI & 7u) || XI < 64 ||
+      XI > (1u << 20) || (uint64_t)XA + 8 < XI || nloc > MSGCAP)
+    return SWIM_EINVAL;
+  if (gossip && ((SLOTS & 63u) || SLOTS < 64 || SLOTS > 4096 || !pow2(BCAP) || BCAP > 64 || LOGW < 1 || LOGW > 8 || F < 1 || F > 8 ||
+                 gossip_t < 1 || EXPB > (1u << 20) || N > (1u << 16)))
+    return SWIM_EINVAL;
+  const KeyPlaneSizes z = key_plane_sizes(N);
+  const uint32_t NCHUNK = z.NCHUNK, MW = z.MW, b = k & 1u, QW = SLOTS / 64;
+  const uint64_t SE = sync_entry_size(MW), b_reg = (uint64_t)W * (iin ? XI : XA);
+  const uint64_t b_in = b_reg + 16ull * W + 4ull * SMW * nloc + (gossip ? 4ull * N * (4 + LOGW) : 0);
+  if (inb != b_in) return SWIM_EINVAL;
+  const uint8_t* i8 = (const uint8_t*)in;
+  const uint8_t *i_reg = i8, *i_rcnt = i_reg + b_reg, *i_scnt = i_rcnt + 8ull * W, *i_mtmp = i_scnt + 8ull * W,
+                *i_first = i_mtmp + 4ull * SMW * nloc, *i_rhead = i_first + 4ull * N, *i_rtail = i_rhead + 4ull * N,
+                *i_lpos = i_rtail + 4ull * N, *i_lspread = i_lpos + 4ull * N;
+  const uint64_t b_core = 4ull * SMW * MSGCAP + 4ull * N + 4ull * MSGCAP + 8ull * RXCAP * MW + 8ull * RXCAP + 4ull * TL * MSGCAP +
+                          4 * 18 + 8ull * W * 2 + 8ull * W + 8ull * W + 16ull * W;
+  const uint64_t b_gos = gossip ? 32ull * SLOTS + 16ull * QW + 2ull * N * SLOTS + 8ull * N * QW + 4ull * N * BCAP + 4ull * N * 8 +
+                                      4ull * N * F + 12ull * N * LOGW + 4ull * N * LOGW * F
+                                : 0;
+  if (outb != b_core + b_gos) return SWIM_EINVAL;
+
+  // ---- host checks: the count words, and every region k_unpack_a will parse, against its byte count ----
+  unsigned long long rcnt[8], scnt[8];
+  memcpy(scnt, i_scnt, 8ull * W);
+  for (uint32_t p = 0; p < W; ++p) {
+    if (iin)
+      memcpy(&rcnt[p], i_reg + (size_t)p * XI, 8);
+    else
+      memcpy(&rcnt[p], i_rcnt + 8ull * p, 8);
+  }
+  bool gate = false, cut = false;  // cut: an inline block that does not hold its whole region
+  for (uint32_t p = 0; p < W; ++p) {
+    if ((rcnt[p] | scnt[p]) & (XFLAG_GOSSIP | XFLAG_OVER) || (scnt[p] & XCNT_MASK) > XI - 8) gate = true;
+    if (p != rank && iin && (rcnt[p] & XCNT_MASK) > XI - 8) cut = true;
+  }
+  if (cut && !(spec && gate)) return SWIM_EINVAL;  // the engine fetches the rest by a send / recv group first
+  const bool parsed = !(spec && (halt || gate));
+  for (uint32_t i = 0; i < nloc; ++i) {
+    SyncMsg mm;
+    memcpy(&mm, i_mtmp + sizeof(SyncMsg) * (size_t)i, sizeof mm);
+    if (mm.dst >= N || mm.src >= N) return SWIM_EINVAL;
+  }
+  if (gossip)
+    for (uint32_t m = 0; m < N; ++m) {
+      uint32_t h, t;
+      memcpy(&h, i_rhead + 4ull * m, 4);
+      memcpy(&t, i_rtail + 4ull * m, 4);
+      if (t - h > BCAP) return SWIM_EINVAL;
+    }
+  for (uint32_t p = 0; parsed && p < W; ++p) {
+    const uint64_t bytes = rcnt[p] & XCNT_MASK;
+    if (p == rank || bytes < 32) continue;
+    if (bytes > XA || (bytes & 7u)) return SWIM_EINVAL;
+    const uint8_t* Rg = i_reg + (size_t)p * (iin ? XI : XA) + (iin ? 8 : 0);
+    uint32_t H[8];
+    memcpy(H, Rg, 32);
+    const uint64_t nslot = H[0], nround = H[1], nsync = H[2], nchunk = H[3], data_off = H[4];
+    if (nslot > 1024 || nround > 1024 || nsync > 4096 || nchunk > (1u << 20) || ((nslot || nround) && !gossip)) return SWIM_EINVAL;
+    const uint64_t e0 = 32 + 4ull * NSW * nslot + 4ull * RRW * nround;
+    if (e0 + SE * nsync > data_off || (data_off & 15u) || data_off + nchunk * CH * 4 > bytes) return SWIM_EINVAL;
+    for (uint64_t i = 0; i < nslot; ++i) {
+      uint32_t r[NSW];
+      memcpy(r, Rg + 32 + 4ull * NSW * i, sizeof r);
+      if (r[0] >= SLOTS || r[7] >= N) return SWIM_EINVAL;
+    }
+    for (uint64_t i = 0; i < nround; ++i) {
+      uint32_t r[RRW];
+      memcpy(r, Rg + 32 + 4ull * NSW * nslot + 4ull * RRW * i, sizeof r);
+      if (r[0] >= N || r[1] > F) return SWIM_EINVAL;
+      for (uint32_t j = 0; j < r[1]; ++j)
+        if (r[4 + j] >= N) return SWIM_EINVAL;
+    }
+    for (uint64_t i = 0; i < nsync; ++i) {
+      const uint8_t* e = Rg + e0 + SE * i;
+      SyncMsg mm;
+      uint32_t base;
+      memcpy(&mm, e, sizeof mm);
+      memcpy(&base, e + sizeof mm, 4);
+      if (mm.dst >= N || mm.src >= N) return SWIM_EINVAL;
+      uint64_t cnt = 0;
+      for (uint32_t q = 0; q < MW; ++q) {
+        uint64_t mk;
+        memcpy(&mk, e + sizeof mm + 8 + 8ull * q, 8);
+        const uint32_t top = NCHUNK - 64 * q >= 64 ? 64 : NCHUNK - 64 * q;
+        if (top < 64 && (mk >> top)) return SWIM_EINVAL;
+        cnt += (uint64_t)__builtin_popcountll(mk);
+      }
+      if (base + cnt > nchunk) return SWIM_EINVAL;
+    }
+  }
+
+  // ---- the Dev: only the fields k_inline_in, k_unpack_a, msgs_commit, slot_create and tick_end read ----
+  Cursor o{(uint8_t*)out};
+  uint8_t *o_msgs = o.take(4ull * SMW * MSGCAP), *o_head = o.take(4ull * N), *o_next = o.take(4ull * MSGCAP),
+          *o_rxm = o.take(8ull * RXCAP * MW), *o_rxo = o.take(8ull * RXCAP), *o_mlog = o.take(4ull * TL * MSGCAP),
+          *o_sc = o.take(4 * 18), *o_scnt = o.take(8ull * W), *o_bscnt = o.take(8ull * W), *o_xdone = o.take(8ull * W),
+          *o_rcnt = o.take(8ull * W), *o_host = o.take(16ull * W);
+  PrimBufs bf;
+  Dev d;
+  memset(&d, 0, sizeof d);
+  d.N = N, d.NS = z.NS, d.NCHUNK = NCHUNK, d.MW = MW, d.W = W, d.rank = rank, d.lo = shard_lo(N, W, rank), d.hi = shard_lo(N, W, rank + 1);
+  d.NL = d.hi - d.lo, d.MSGCAP = MSGCAP, d.RXCAP = RXCAP, d.ARENA_ROWS = AR, d.XA_PEER = XA, d.XI = XI;
+  d.ackres = ackres ? ACKRES_ON : 0u;
+  d.xa_recv = bf.get<uint8_t>((uint64_t)W * XA, iin ? nullptr : i_reg, iin ? 0 : (uint64_t)W * XA);
+  uint8_t* irecv = iin ? bf.get<uint8_t>(b_reg, i_reg, b_reg) : nullptr;
+  if (iin && bf.rc == SWIM_OK && hipMemset(d.xa_recv, (int)(sent & 0xFF), (uint64_t)W * XA) != hipSuccess) bf.rc = SWIM_EDEVICE;
+  d.xa_rcnt = bf.get<unsigned long long>(W, iin ? o_rcnt : i_rcnt, W);
+  d.xa_scnt = bf.get<unsigned long long>(W, i_scnt, W);
+  d.xb_scnt = bf.get<unsigned long long>(W, o_bscnt, W);
+  d.xi_host = bf.get<unsigned long long>(2ull * W, o_host, 2ull * W);
+  d.xdone = bf.get<uint32_t>(2ull * W, o_xdone, 2ull * W);
+  d.mtmp = (SyncMsg*)bf.get<uint32_t>((uint64_t)SMW * MSGCAP, i_mtmp, (uint64_t)SMW * nloc);
+  d.msgs[b] = (SyncMsg*)bf.get<uint32_t>((uint64_t)SMW * MSGCAP, o_msgs, (uint64_t)SMW * MSGCAP);
+  std::vector<uint32_t> never(std::max<uint64_t>(2ull * N, 2ull * MSGCAP), NEVER);
+  d.m_head = bf.get<uint32_t>(2ull * N, never.data(), 2ull * N);  // reset by the consumer: every list is empty
+  d.m_next = bf.get<uint32_t>(2ull * MSGCAP, o_next, MSGCAP);
+  if (bf.rc == SWIM_OK && hipMemcpy(d.m_next + MSGCAP, o_next, 4ull * MSGCAP, hipMemcpyHostToDevice) != hipSuccess) bf.rc = SWIM_EDEVICE;
+  d.rx_mask = bf.get<uint64_t>((uint64_t)RXCAP * MW, o_rxm, (uint64_t)RXCAP * MW);
+  d.rx_off = bf.get<uint64_t>(RXCAP, o_rxo, RXCAP);
+  d.mlog = bf.get<uint32_t>((uint64_t)TL * MSGCAP, o_mlog, (uint64_t)TL * MSGCAP);
+  // the counters: the words the launch owns start where a tick leaves them, the ones it may reset at the sentinel
+  uint32_t sc[18] = {sent, sent, 0, 0, sent, sent, sent, sent, nloc, 0, 0, sent, 0, 0, sent, sent, sent, sent};
+  sc[2 + b] = 0, sc[2 + (b ^ 1u)] = sent;  // arena_used: this tick's pins count from 0
+  d.nmsg = bf.get<uint32_t>(2, sc, 2);
+  d.arena_used = bf.get<uint32_t>(2, sc + 2, 2);
+  d.xn = bf.get<uint32_t>(8, sc + 4, 8);
+  d.err = bf.get<uint32_t>(8);
+  d.ctr_sh = bf.get<unsigned long long>((size_t)CSH * CSTRIDE);
+  d.halt = (uint32_t*)(d.ctr_sh + SH_HALT);
+  const uint32_t h1 = halt ? 1u : 0u;
+  if (bf.rc == SWIM_OK && hipMemcpy(d.halt, &h1, 4, hipMemcpyHostToDevice) != hipSuccess) bf.rc = SWIM_EDEVICE;
+  d.pool_used = bf.get<uint32_t>(1, sc + 14, 1);
+  d.rc_n = bf.get<uint32_t>(1, sc + 15, 1);
+  d.ndl = bf.get<uint32_t>(1, sc + 16, 1);
+  d.ndlw = bf.get<uint32_t>(1, sc + 17, 1);
+  uint8_t *o_gid = nullptr, *o_key = nullptr, *o_slot4 = nullptr, *o_gu = nullptr, *o_S = nullptr, *o_hb = nullptr, *o_rg = nullptr,
+          *o_mem = nullptr, *o_T = nullptr, *o_log = nullptr, *o_tg = nullptr;
+  uint32_t* mem8 = nullptr;  // [8][N]: rtail, held, tround, tcnt, tspread, tperiod, spchg, log_pos
+  uint32_t* slot4 = nullptr;  // [4][SLOTS]: subj, ctick, exp, used
+  uint32_t* log3 = nullptr;  // [3][N][LOGW]: tick, spread, cnt
+  if (gossip) {
+    o_gid = o.take(8ull * SLOTS), o_key = o.take(8ull * SLOTS), o_slot4 = o.take(16ull * SLOTS), o_gu = o.take(16ull * QW);
+    o_S = o.take(2ull * N * SLOTS), o_hb = o.take(8ull * N * QW), o_rg = o.take(4ull * N * BCAP), o_mem = o.take(32ull * N);
+    o_T = o.take(4ull * N * F), o_log = o.take(12ull * N * LOGW), o_tg = o.take(4ull * N * LOGW * F);
+    d.SLOTS = SLOTS, d.QW = QW, d.BCAP = BCAP, d.LOGW = LOGW, d.F = F, d.EXPB = EXPB, d.gossip_t = gossip_t, d.gt_mul = gt_mul_of(gossip_t);
+    d.slot_gid = bf.get<uint64_t>(SLOTS, o_gid, SLOTS);
+    d.slot_key = bf.get<uint64_t>(SLOTS, o_key, SLOTS);
+    slot4 = bf.get<uint32_t>(4ull * SLOTS, o_slot4, 4ull * SLOTS);
+    d.slot_subj = slot4, d.slot_ctick = slot4 + SLOTS, d.slot_exp = slot4 + 2 * SLOTS, d.slot_used = slot4 + 3 * SLOTS;
+    d.GU = bf.get<unsigned long long>(2ull * QW);  // the bit planes are set with atomicOr: they start empty
+    d.DM = d.GU + QW;
+    d.S = bf.get<uint16_t>((uint64_t)N * SLOTS, o_S, (uint64_t)N * SLOTS);
+    d.HB = bf.get<unsigned long long>((uint64_t)N * QW);
+    d.rg = bf.get<uint32_t>((uint64_t)N * BCAP, o_rg, (uint64_t)N * BCAP);
+    d.firstGossip = bf.get<uint32_t>(N, i_first, N);
+    d.rhead = bf.get<uint32_t>(N, i_rhead, N);
+    mem8 = bf.get<uint32_t>(8ull * N, o_mem, 8ull * N);
+    d.rtail = mem8, d.held = mem8 + N, d.tround = mem8 + 2ull * N, d.tcnt = mem8 + 3ull * N, d.tspread = mem8 + 4ull * N;
+    d.tperiod = mem8 + 5ull * N, d.spchg = mem8 + 6ull * N, d.log_pos = mem8 + 7ull * N;
+    if (bf.rc == SWIM_OK && (hipMemcpy(d.rtail, i_rtail, 4ull * N, hipMemcpyHostToDevice) != hipSuccess ||
+                             hipMemset(d.held, 0, 4ull * N) != hipSuccess ||
+                             hipMemcpy(d.log_pos, i_lpos, 4ull * N, hipMemcpyHostToDevice) != hipSuccess))
+      bf.rc = SWIM_EDEVICE;
+    d.T = bf.get<uint32_t>((uint64_t)N * F, o_T, (uint64_t)N * F);
+    log3 = bf.get<uint32_t>(3ull * N * LOGW, o_log, 3ull * N * LOGW);
+    d.log_tick = log3, d.log_spread = log3 + (uint64_t)N * LOGW, d.log_cnt = log3 + 2ull * N * LOGW;
+    if (bf.rc == SWIM_OK && hipMemcpy(d.log_spread, i_lspread, 4ull * N * LOGW, hipMemcpyHostToDevice) != hipSuccess) bf.rc = SWIM_EDEVICE;
+    d.log_tg = bf.get<uint32_t>((uint64_t)N * LOGW * F, o_tg, (uint64_t)N * LOGW * F);
+  }
+  if (bf.rc != SWIM_OK) return bf.rc;
+
+  if (iin)  // launch_inline_in's grid and arguments
+    hipLaunchKernelGGL(k_inline_in, dim3(W), dim3(256), 0, 0, irecv, d.xa_recv, (uint64_t)XA, d.xa_scnt, d.xa_rcnt, d.xi_host, W,
+                       spec ? (const uint32_t*)d.halt : nullptr, XI);
+  hipLaunchKernelGGL(k_unpack_a, dim3(32, W), dim3(256), 0, 0, d, k, end ? 1u : 0u, spec ? 1u : 0u);  // launch_tick_b's grid
+  if (!bf.ran()) return bf.rc;
+
+  bf.back(o_msgs, d.msgs[b], 4ull * SMW * MSGCAP);
+  bf.back(o_head, d.m_head + (size_t)b * N, 4ull * N);
+  bf.back(o_next, d.m_next + (size_t)b * MSGCAP, 4ull * MSGCAP);
+  bf.back(o_rxm, d.rx_mask, 8ull * RXCAP * MW);
+  bf.back(o_rxo, d.rx_off, 8ull * RXCAP);
+  bf.back(o_mlog, d.mlog, 4ull * TL * MSGCAP);
+  bf.back(sc, d.nmsg, 8);
+  bf.back(sc + 2, d.arena_used, 8);
+  bf.back(sc + 4, d.xn, 32);
+  bf.back(sc + 12, d.err, 4);
+  bf.back(sc + 13, d.halt, 4);
+  bf.back(sc + 14, d.pool_used, 4);
+  bf.back(sc + 15, d.rc_n, 4);
+  bf.back(sc + 16, d.ndl, 4);
+  bf.back(sc + 17, d.ndlw, 4);
+  memcpy(o_sc, sc, sizeof sc);
+  bf.back(o_scnt, d.xa_scnt, 8ull * W);
+  bf.back(o_bscnt, d.xb_scnt, 8ull * W);
+  bf.back(o_xdone, d.xdone, 8ull * W);
+  bf.back(o_rcnt, d.xa_rcnt, 8ull * W);
+  bf.back(o_host, d.xi_host, 16ull * W);
+  if (gossip) {
+    bf.back(o_gid, d.slot_gid, 8ull * SLOTS);
+    bf.back(o_key, d.slot_key, 8ull * SLOTS);
+    bf.back(o_slot4, slot4, 16ull * SLOTS);
+    bf.back(o_gu, d.GU, 16ull * QW);
+    bf.back(o_S, d.S, 2ull * N * SLOTS);
+    bf.back(o_hb, d.HB, 8ull * N * QW);
+    bf.back(o_rg, d.rg, 4ull * N * BCAP);
+    bf.back(o_mem, mem8, 32ull * N);
+    bf.back(o_T, d.T, 4ull * N * F);
+    bf.back(o_log, log3, 12ull * N * LOGW);
+    bf.back(o_tg, d.log_tg, 4ull * N * LOGW * F);
+  }
+  return bf.rc;
+}
+
+int prim_inline_in(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 4) return SWIM_EINVAL;
+  const uint32_t W = P[0], XI = P[1], cap = P[2], fl = P[3];  // fl: 1 a speculative launch, 2 its halt word is raised
+  if (W < 2 || W > 8 || (XI & 7u) || XI < 64 || XI > (1u << 20) || (cap & 7u) || (uint64_t)cap + 8 < XI || cap > (1u << 24) ||
+      fl > 3 || fl == 2 || inb != (uint64_t)W * XI + 8ull * W || outb != (uint64_t)W * cap + 24ull * W)
+    return SWIM_EINVAL;
+  const uint8_t* i8 = (const uint8_t*)in;
+  uint8_t* o8 = (uint8_t*)out;
+  PrimBufs bf;
+  uint8_t* irecv = bf.get<uint8_t>((uint64_t)W * XI, i8, (uint64_t)W * XI);
+  unsigned long long* scnt = bf.get<unsigned long long>(W, i8 + (uint64_t)W * XI, W);
+  uint8_t* recv = bf.get<uint8_t>((uint64_t)W * cap, o8, (uint64_t)W * cap);
+  unsigned long long* rcnt = bf.get<unsigned long long>(W, o8 + (uint64_t)W * cap, W);
+  unsigned long long* host = bf.get<unsigned long long>(2ull * W, o8 + (uint64_t)W * cap + 8ull * W, 2ull * W);
+  const uint32_t hw[HALT_WORDS] = {fl & 2u ? 1u : 0u, 0, 0, 0, 0};
+  uint32_t* halt = bf.get<uint32_t>(HALT_WORDS, hw, HALT_WORDS);
+  if (bf.rc != SWIM_OK) return bf.rc;
+  hipLaunchKernelGGL(k_inline_in, dim3(W), dim3(256), 0, 0, irecv, recv, (uint64_t)cap, scnt, rcnt, host, W,
+                     fl & 1u ? (const uint32_t*)halt : nullptr, XI);  // launch_inline_in's grid
+  if (bf.ran() && bf.back(o8, recv, (uint64_t)W * cap) && bf.back(o8 + (uint64_t)W * cap, rcnt, 8ull * W))
+    bf.back(o8 + (uint64_t)W * cap + 8ull * W, host, 16ull * W);
+  return bf.rc;
+}
+
 }  // namespace
 }  // namespace swim
 
 extern "C" int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t n_params, const void* in, size_t in_bytes,
                                     void* out, size_t out_bytes, uint32_t device) {
   using namespace swim;
-  if (op > SWIM_PRIM_SYNC_DIFF || !params || n_params > 16 || !out || (in_bytes && !in) || ((uintptr_t)in & 7u) ||
+  if (op > SWIM_PRIM_XUNPACK || !params || n_params > 32 || !out || (in_bytes && !in) || ((uintptr_t)in & 7u) ||
       ((uintptr_t)out & 7u))
     return SWIM_EINVAL;
   int ndev = 0;
@@ -666,6 +1055,10 @@ extern "C" int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t 
     case SWIM_PRIM_ARITH: return prim_arith(params, n_params, i32, in_bytes, o32, out_bytes);
     case SWIM_PRIM_FEISTEL: return prim_feistel(params, n_params, in_bytes, o32, out_bytes);
     case SWIM_PRIM_RING_MOVE: return prim_ring_move(params, n_params, i32, in_bytes, o32, out_bytes);
-    default: return prim_sync_diff(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_SYNC_DIFF: return prim_sync_diff(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_XPACK: return prim_xpack(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_PACK_B: return prim_pack_b(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_INLINE_IN: return prim_inline_in(params, n_params, i32, in_bytes, o32, out_bytes);
+    default: return prim_xunpack(params, n_params, i32, in_bytes, o32, out_bytes);
   }
 }

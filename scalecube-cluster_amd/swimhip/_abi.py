@@ -252,7 +252,11 @@ DEBUG_SIGNATURES = {
 }
 # swim_debug_prim_eval: ops, and the sub-ops of PRIM_WAVE and PRIM_ARITH (include/swimhip_debug.h has the layouts)
 (PRIM_SCAN, PRIM_SEG_SORT, PRIM_ROUTING, PRIM_WAVE, PRIM_DIRTY, PRIM_ARITH, PRIM_FEISTEL, PRIM_RING_MOVE,
- PRIM_SYNC_DIFF) = range(9)
+ PRIM_SYNC_DIFF, PRIM_XPACK, PRIM_PACK_B, PRIM_INLINE_IN, PRIM_XUNPACK) = range(13)
+# PRIM_XPACK's flags (SWIM_PRIM_XP_*)
+(XP_ACKRES, XP_INLINE, XP_SPEC, XP_HALTED, XP_TLOG, XP_INLINE_OUT) = (1, 2, 4, 8, 16, 32)
+# PRIM_XUNPACK's flags (SWIM_PRIM_XU_*)
+(XU_END, XU_SPEC, XU_HALTED, XU_ACKRES, XU_INLINE_IN, XU_GOSSIP) = (1, 2, 4, 8, 16, 32)
 # PRIM_SYNC_DIFF's flags (SWIM_PRIM_SD_*)
 (SD_K8, SD_LISTER, SD_LISTS, SD_SHARDED, SD_DIRTY) = (1, 2, 4, 8, 16)
 (WAVE_APPEND, WAVE_RESERVE, WAVE_BLOCK_RESERVE, WAVE_SUM32, WAVE_MIN32, WAVE_SUM64) = range(6)

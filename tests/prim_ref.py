@@ -753,3 +753,733 @@ def sd_expect(case, narrow, wide):
                     if g < z["NMETA"]:
                         exp[i]["segs"][g] = np.zeros(0, np.uint64)
     return exp, differed
+
+
+# ---------------------------------------------------------------------------------------------- row-shard exchange codec
+# References for k_pack_all, k_pack_b, k_inline_out and k_inline_in (tests/test_gpu_exchange.py; SWIM_PRIM_XPACK, PACK_B,
+# INLINE_IN), written from the layout shard.hip's header comment states:
+#   region A: u32 hdr[8] = {nslot, nround, nsync, nchunk, data_off, 0, 0, 0}; slot records [8 words]; round records
+#   [12 words]; SYNC entries {SyncMsg, u32 chunk base, u32 0, u64 mask[MW], u32 log[16]}; chunks of 2048 keys at data_off,
+#   which is the entries' end rounded up to 256.
+# Everything the packer does not write keeps the caller's preset byte, so a comparison is equality of whole buffers.
+SM_FIELDS = ("src", "dst", "kind", "seq", "cid_iss", "cid_cnt", "payload", "psize", "ncand", "pad", "pin", "due", "tln")
+SMW = len(SM_FIELDS)          # words of a SyncMsg (engine.h; tests/test_prim_ref.py reads the struct's text)
+NSW, RRW = 8, 12              # words of a new-slot and of a round record
+XCNT_MASK, XFLAG_GOSSIP, XFLAG_OVER = (1 << 48) - 1, 1 << 62, 1 << 61
+E_MSGS, E_ARENA, E_XCAP = 32, 64, 1 << 17
+XP_ACKRES, XP_INLINE, XP_SPEC, XP_HALTED, XP_TLOG, XP_INLINE_OUT = 1, 2, 4, 8, 16, 32
+XP_BYTE = 0xA5                # the preset of every output byte
+XP_WORD, XP_WORD64 = 0xA5A5A5A5, 0xA5A5A5A5A5A5A5A5
+
+
+def shard_lo(N, W, r):
+    """First member of shard r: contiguous ranges floor(r N / W)."""
+    return r * N // W
+
+
+def shard_of(N, W, m):
+    return max(r for r in range(W) if shard_lo(N, W, r) <= m)
+
+
+def sync_entry_size(MW):
+    return 4 * SMW + 8 + 8 * MW + 4 * TL
+
+
+def xp_msg(i, src, dst, kind=1, payload=NEVER, tln=0):
+    """A whole SyncMsg; the fields the packer only carries get distinct values derived from i."""
+    return dict(src=src, dst=dst, kind=kind, seq=1000 + i, cid_iss=(7 * i + 3) & M32, cid_cnt=i ^ 0x55, payload=payload,
+                psize=17 + i, ncand=0x00C0FFEE, pad=0x0BAD0000 | i, pin=NEVER, due=0x0D0E0000 | i, tln=tln)
+
+
+def msg_words(m):
+    return u32([m[f] for f in SM_FIELDS])
+
+
+def mask_chunks(mask):
+    return [c for c in range(mask.bit_length()) if (mask >> c) & 1]
+
+
+def xp_payload(c, m):
+    """(keys, dirty mask) of message m's payload on the sending rank."""
+    lo = shard_lo(c["N"], c["W"], c["rank"])
+    if m["payload"] == NEVER:
+        return c["rows"][m["src"] - lo], c["rdirty"][m["src"] - lo]
+    return c["arena"][m["payload"]], c["arena_dirty"][m["payload"]]
+
+
+def xpack_ref(c):
+    """What k_pack_all leaves in buffers preset to XP_BYTE: xa_send uint8[W][XA_PEER], xa_scnt uint64[W], xi_send and
+    xi_out (k_inline_out on the same regions) uint8[W][XI], mtmp[MSGCAP][13], mlog[MSGCAP][16], xn[8], err; and per peer
+    the region's parts, for the field-by-field comparisons: regions[q] = dict(fits, bytes, nslot, nround, nsync, nchunk,
+    off_sync, data_off, entries = [(message index, chunk base, mask, log words shipped)]); None for the own rank."""
+    z = sd_sizes(c["N"])
+    N, W, rank, NS, MW, fl = c["N"], c["W"], c["rank"], z["NS"], z["MW"], c["flags"]
+    XA, XI, CAP = c["XA_PEER"], c["XI"], c["MSGCAP"]
+    lo = shard_lo(N, W, rank)
+    out = dict(xa_send=np.full((W, XA), XP_BYTE, np.uint8), xa_scnt=np.full(W, XP_WORD64, np.uint64),
+               xi_send=np.full((W, XI), XP_BYTE, np.uint8), xi_out=np.full((W, XI), XP_BYTE, np.uint8),
+               mtmp=np.full((CAP, SMW), XP_WORD, np.uint32), mlog=np.full((CAP, TL), XP_WORD, np.uint32),
+               xn=u32([c["xn0"], c["xn1"], XP_WORD, XP_WORD, c["xn4"], XP_WORD, XP_WORD, XP_WORD]), err=0, regions=[None] * W)
+    xa, scnt, xi = out["xa_send"], out["xa_scnt"], out["xi_send"]
+    halted = bool(fl & XP_SPEC and fl & XP_HALTED)
+    if not halted:
+        msgs = list(enumerate(c["msgs"]))[:CAP]
+        ackres = bool(fl & XP_ACKRES)
+
+        def log_prefix(m):  # a resolvable SYNC_ACK's sender's write-log prefix; nothing for the other messages
+            n = m["tln"] if m["kind"] & KF_RES and m["tln"] <= TL else 0
+            return c["tlog"][m["src"] - lo][:n] if n else u32([])
+
+        nslot, nround = min(c["xn0"], c["NSCAP"]), min(c["xn1"], c["RRCAP"])
+        SE = sync_entry_size(MW)
+        for q in range(W):
+            sel = [(i, m) for i, m in msgs if shard_of(N, W, m["dst"]) == q]
+            if q == rank:  # the local column: straight to the next tick's inbound list, in message order
+                for j, (i, m) in enumerate(sel, start=c["xn4"]):
+                    if j < CAP:
+                        out["mtmp"][j] = msg_words(m)
+                        if ackres:
+                            lp = log_prefix(m)
+                            out["mlog"][j][:len(lp)] = lp
+                    elif j == CAP:
+                        out["err"] |= E_MSGS
+                out["xn"][4] = (c["xn4"] + len(sel)) & M32
+                if fl & XP_INLINE:
+                    xi[q][:8] = 0
+                continue
+            nsync, nchunk = len(sel), sum(bin(xp_payload(c, m)[1]).count("1") for _, m in sel)
+            off_sync = 32 + 4 * NSW * nslot + 4 * RRW * nround
+            data_off = -(-(off_sync + SE * nsync) // 256) * 256
+            total = data_off + nchunk * CH * 4
+            fits = nsync <= c["RQCAP"] and total <= XA and nchunk <= c["CHCAP"]
+            reg = dict(fits=fits, bytes=total if fits else 32, nslot=nslot if fits else 0, nround=nround if fits else 0,
+                       nsync=nsync if fits else 0, nchunk=nchunk if fits else 0, off_sync=off_sync,
+                       data_off=data_off if fits else 256, entries=[])
+            out["regions"][q] = reg
+            if not fits:
+                out["err"] |= E_XCAP
+            xa[q][:32] = u32([reg["nslot"], reg["nround"], reg["nsync"], reg["nchunk"], reg["data_off"], 0, 0, 0]).view(np.uint8)
+            scnt[q] = reg["bytes"] | (XFLAG_GOSSIP if c["used"] > 0 else 0)
+            if not fits:
+                continue
+            rec = np.concatenate([u32(c["ns_rec"]).reshape(-1)[:NSW * nslot], u32(c["rr_rec"]).reshape(-1)[:RRW * nround]])
+            xa[q][32:off_sync] = u32(rec).view(np.uint8)
+            base = 0
+            for j, (i, m) in enumerate(sel):
+                keys, mask = xp_payload(c, m)
+                lp = log_prefix(m) if ackres else u32([])
+                e = np.concatenate([msg_words(m), u32([base, 0]),
+                                    u32([(mask >> (32 * w)) & M32 for w in range(2 * MW)]), u32(lp)])
+                o = off_sync + SE * j
+                xa[q][o:o + 4 * len(e)] = e.view(np.uint8)
+                reg["entries"].append((i, base, mask, len(lp)))
+                for c_ in mask_chunks(mask):  # the payload's dirty chunks in ascending order; the last one may be partial
+                    n = min(CH, NS - c_ * CH)
+                    o = data_off + base * CH * 4
+                    xa[q][o:o + 4 * n] = u32(keys[c_ * CH:c_ * CH + n]).view(np.uint8)
+                    base += 1
+            assert base == nchunk
+        if fl & XP_INLINE:  # the count word, then the region's head; OVER on every peer's word if any region is past it
+            over = any(q != rank and (int(scnt[q]) & XCNT_MASK) > XI - 8 for q in range(W))
+            for q in range(W):
+                if q != rank:
+                    word = int(scnt[q]) | (XFLAG_OVER if over else 0)
+                    n = min(word & XCNT_MASK, XI - 8)
+                    xi[q][:8] = np.array([word], np.uint64).view(np.uint8)
+                    xi[q][8:8 + n] = xa[q][:n]
+    for q in range(W):  # k_inline_out: the same block from the same region and count word, without the OVER mark
+        n = min(int(scnt[q]) & XCNT_MASK, XI - 8)
+        out["xi_out"][q][:8] = np.array([scnt[q]], np.uint64).view(np.uint8)
+        out["xi_out"][q][8:8 + n] = xa[q][:n]
+    return out
+
+
+def xp_pack(c, inline_out=True):
+    """(params, in, out) of a SWIM_PRIM_XPACK call; out is preset to XP_BYTE."""
+    z = sd_sizes(c["N"])
+    MW, CAP, W = z["MW"], c["MSGCAP"], c["W"]
+    words64 = lambda masks: np.array([[(m >> (64 * w)) & M64 for w in range(MW)] for m in masks], np.uint64).reshape(-1)
+    parts = [words64(c["rdirty"]), words64(c["arena_dirty"]), u32(c["rows"]), u32(c["arena"]),
+             u32([msg_words(m) for m in c["msgs"]]).reshape(-1)]
+    fl = c["flags"] | (XP_INLINE_OUT if inline_out else 0)
+    if c["tlog"] is not None:
+        parts.append(u32(c["tlog"]))
+        fl |= XP_TLOG
+    parts += [u32(c["ns_rec"]).reshape(-1), u32(c["rr_rec"]).reshape(-1)]
+    raw = b"".join(np.ascontiguousarray(a).tobytes() for a in parts)
+    inp = np.frombuffer(raw + b"\0" * (-len(raw) % 8 + 8), np.uint64).copy()  # 8-byte aligned, whatever its length
+    nin = len(raw)
+    params = [c["N"], W, c["rank"], len(c["rows"]), c["b"], fl, len(c["msgs"]), CAP, len(c["arena"]), c["NSCAP"], c["RRCAP"],
+              c["RQCAP"], c["CHCAP"], c["XA_PEER"], c["XI"], c["used"], c["xn0"], c["xn1"], len(c["ns_rec"]), len(c["rr_rec"]),
+              c["xn4"], XP_WORD]
+    nout = W * c["XA_PEER"] + 8 * W + 2 * W * c["XI"] + 4 * (SMW * CAP + TL * CAP + 10)
+    return params, inp.view(np.uint8)[:nin], np.full(nout // 8 + 1, XP_WORD64, np.uint64).view(np.uint8)[:nout]
+
+
+def xp_unpack(c, out):
+    W, XA, XI, CAP = c["W"], c["XA_PEER"], c["XI"], c["MSGCAP"]
+    pos = [0]
+
+    def take(nbytes, dtype=np.uint8):
+        a = out[pos[0]:pos[0] + nbytes]
+        pos[0] += nbytes
+        return np.frombuffer(a.tobytes(), dtype=dtype)
+
+    r = dict(xa_send=take(W * XA).reshape(W, XA), xa_scnt=take(8 * W, np.uint64), xi_send=take(W * XI).reshape(W, XI),
+             xi_out=take(W * XI).reshape(W, XI), mtmp=take(4 * SMW * CAP, np.uint32).reshape(CAP, SMW),
+             mlog=take(4 * TL * CAP, np.uint32).reshape(CAP, TL), xn=take(32, np.uint32))
+    tail = take(8, np.uint32)
+    r.update(err=int(tail[0]), halt=int(tail[1]))
+    assert pos[0] == len(out)
+    return r
+
+
+def xp_rows(N, specs, seed):
+    """(base_row, rows, masks): a baseline row of present keys (padding 0) and one row per spec = (chunks that differ from
+    the baseline, chunks marked dirty although equal). A mask bit is set iff the chunk differs, plus the extra bits; a
+    differing chunk differs in its first and last key and in one between."""
+    z = sd_sizes(N)
+    rng = np.random.default_rng(seed)
+    base = np.zeros(z["NS"], np.uint32)  # the same for every case of one N: the ranks of a cluster share the baseline
+    base[:N] = (np.random.default_rng(7000 + N).integers(1, 2**20, N).astype(np.uint32) << np.uint32(2)) | np.uint32(1)
+    rows, masks = [], []
+    for differ, extra in specs:
+        row = base.copy()
+        for c_ in differ:
+            a, b = c_ * CH, min((c_ + 1) * CH, N)
+            for s in {a, b - 1, a + int(rng.integers(0, b - a))}:
+                row[s] += np.uint32(4 * int(rng.integers(1, 100)))
+        rows.append(row)
+        masks.append(sum(1 << c_ for c_ in set(differ) | set(extra)))
+    return base, np.array(rows, np.uint32).reshape(len(specs), z["NS"]), masks
+
+
+def xp_case(N, W, rank, rows, arena, msgs, seed, **kw):
+    """A case with the capacities an engine that is not at capacity has (every region fits, one spare message), unless
+    kw says otherwise. rows / arena: specs of xp_rows."""
+    z = sd_sizes(N)
+    base, allrows, masks = xp_rows(N, list(rows) + list(arena), seed)
+    R = len(rows)
+    rng = np.random.default_rng(seed + 1)
+    c = dict(N=N, W=W, rank=rank, b=seed & 1, flags=0, base=base, rows=allrows[:R], rdirty=masks[:R], arena=allrows[R:],
+             arena_dirty=masks[R:], msgs=msgs, MSGCAP=len(msgs) + 1, NSCAP=4, RRCAP=4, RQCAP=len(msgs) + 1, CHCAP=4096,
+             XI=16384, used=0, xn0=0, xn1=0, xn4=0, ns_rec=np.zeros((0, NSW), np.uint32), rr_rec=np.zeros((0, RRW), np.uint32),
+             tlog=rng.integers(0, N, (R, TL)).astype(np.uint32))
+    c.update(kw)
+    if "XA_PEER" not in c:
+        nch = sum(bin(xp_payload(c, m)[1]).count("1") for m in msgs)
+        head = 32 + 4 * NSW * c["NSCAP"] + 4 * RRW * c["RRCAP"] + sync_entry_size(z["MW"]) * len(msgs)
+        c["XA_PEER"] = max(-(-head // 256) * 256 + 256 + nch * CH * 4, -(-c["XI"] // 16) * 16)  # k_inline_out reads XI - 8
+    return c
+
+
+def xp_records(N, slots, cnts, seed, origins=None, members=None):
+    """(ns_rec, rr_rec): new-slot records {slot, gid lo, gid hi, subject, tick, key lo, key hi, origin} and round records
+    {member, cnt, spread, period, targets[8]} with the given target counts; the targets past cnt are noise that the
+    packer ships as it is."""
+    rng = np.random.default_rng(seed)
+    ns = u32([[g, int(rng.integers(0, 2**32)), int(rng.integers(0, 2**32)), int(rng.integers(0, N)), 40, int(rng.integers(0, 2**30)),
+               int(rng.integers(1, 4)), origins[i] if origins else int(rng.integers(0, N))] for i, g in enumerate(slots)]).reshape(-1, NSW)
+    rr = u32([[members[i] if members else int(rng.integers(0, N)), n, 3 + i, 10 + i] + [int(t) for t in rng.integers(0, N, 8)]
+              for i, n in enumerate(cnts)])
+    return ns, rr.reshape(-1, RRW)
+
+
+def _n2049_msgs():
+    # rank 1 of N = 2049, W = 3 owns 683 .. 1365; rows 683 .. 688
+    return [xp_msg(0, 683, 5), xp_msg(1, 684, 1400), xp_msg(2, 685, 7), xp_msg(3, 686, 2000), xp_msg(4, 686, 700),
+            xp_msg(5, 687, 100), xp_msg(6, 683, 1500, payload=0), xp_msg(7, 688, 0, kind=2, payload=1), xp_msg(8, 688, 2048),
+            xp_msg(9, 684, 1365), xp_msg(10, 685, 682), xp_msg(11, 686, 1366, kind=2)]
+
+
+N2049_ROWS = [([], []), ([0], []), ([1], []), ([0, 1], []), ([], [1]), ([0], [1])]
+N2049_ARENA = [([1], []), ([], [])]
+
+
+def xpack_cases():
+    """{name: case}: the smallest shapes that reach each edge of k_pack_all (tests/test_prim_ref.py asserts that each one
+    does). A region of k_pack_all is a multiple of 256 B (or 32 B after an overflow), so the inline edges are reached by
+    moving XI around a 256-B region: XI = 272, 264, 256, 248 put it at XI - 16, XI - 8, XI and XI + 8."""
+    out = {}
+    # NS = 8: one chunk, and that one partial; a local, a peer and a local destination
+    out["n5-w2"] = xp_case(5, 2, 0, [([0], []), ([], [])], [], [xp_msg(0, 0, 1), xp_msg(1, 0, 3), xp_msg(2, 1, 0)], 51)
+    # NS = 2056: the second chunk has 8 keys; clean, one-chunk and two-chunk payloads, live and arena rows, records
+    ns, rr = xp_records(2049, [5, 64, 127], [0, 1, 8], 52, origins=[700, 700, 1000], members=[683, 684, 1365])
+    big = dict(ns_rec=ns, rr_rec=rr, xn0=3, xn1=3, used=3, flags=XP_INLINE)
+    out["n2049-w3-r1"] = xp_case(2049, 3, 1, N2049_ROWS, N2049_ARENA, _n2049_msgs(), 53, **big)
+    out["n2049-clamped"] = xp_case(2049, 3, 1, N2049_ROWS, N2049_ARENA, _n2049_msgs(), 53, **dict(big, NSCAP=2, RRCAP=1, xn0=9, xn1=3,
+                                   ns_rec=ns[:2], rr_rec=rr[:1]))
+    out["spec-halted"] = xp_case(2049, 3, 1, N2049_ROWS, N2049_ARENA, _n2049_msgs(), 53, **dict(big, flags=XP_INLINE | XP_SPEC | XP_HALTED))
+    out["spec-runs"] = xp_case(2049, 3, 1, N2049_ROWS, N2049_ARENA, _n2049_msgs(), 53, **dict(big, flags=XP_INLINE | XP_SPEC))
+    # three batches of the block scans: 600 messages to the peer, 300 local, dirty payloads around the batch edges
+    dirty_src = {255: 4, 256: 5, 257: 6, 511: 7, 512: 4, 2: 5, 700: 6, 898: 4}
+    msgs = []
+    for i in range(900):
+        local = (i % 3 == 0 and i != 255) or i == 1
+        msgs.append(xp_msg(i, dirty_src.get(i, i % 4), (i * 5) % 2050 if local else 2050 + (i * 7) % 2050))
+    rows = [([], [])] * 4 + [([0, 1, 2], []), ([0, 2], []), ([1], []), ([2], [0])]
+    out["n4100-batches"] = xp_case(4100, 2, 0, rows, [], msgs, 54, flags=XP_INLINE)
+    # MW = 2, NCHUNK = 65: mask bits 0, 63 and 64; a message to every peer but shard 5, which gets a header only
+    lo = shard_lo(131073, 8, 3)
+    rows = [([0], []), ([63], []), ([64], []), ([0, 63, 64], [])]
+    msgs = [xp_msg(0, lo, 0), xp_msg(1, lo + 1, 16384), xp_msg(2, lo + 2, 49151), xp_msg(3, lo + 3, 65536), xp_msg(4, lo, lo + 10),
+            xp_msg(5, lo + 1, 98304, payload=0), xp_msg(6, lo + 3, 131072), xp_msg(7, lo + 2, 100), xp_msg(8, lo + 1, 70000)]
+    out["n131073-w8-r3"] = xp_case(131073, 8, 3, rows, [([63, 64], [])], msgs, 55, flags=XP_INLINE)
+    # the inline block's edges: a 256-B region (one clean message) against XI; XI = 64 is the floor of the xinl capacity
+    for XI in (272, 264, 256, 248, 64):
+        out[f"inl-xi{XI}"] = xp_case(5, 2, 0, [([], [])], [], [xp_msg(0, 0, 4)], 56, flags=XP_INLINE, XI=XI)
+    out["inl-off"] = xp_case(5, 2, 0, [([], [])], [], [xp_msg(0, 0, 4)], 56, flags=0, XI=248)
+    # one of two peers over: shard 1 gets 256 B = XI - 8, shard 2 a chunk more; the OVER mark must land on both
+    out["inl-one-over"] = xp_case(5, 3, 0, [([0], [])], [([], [])], [xp_msg(0, 0, 1, payload=0), xp_msg(1, 0, 3)], 57,
+                                  flags=XP_INLINE, XI=264)
+    # overflows: the region that does not fit is a header of zero counts, the other peer's is complete
+    m3 = [xp_msg(0, 683, 1), xp_msg(1, 683, 2), xp_msg(2, 683, 3), xp_msg(3, 684, 1400)]
+    out["ovf-rqcap"] = xp_case(2049, 3, 1, N2049_ROWS, [], m3, 58, flags=XP_INLINE, RQCAP=2, MSGCAP=8)
+    m2 = [xp_msg(0, 686, 1), xp_msg(1, 684, 1400)]
+    out["ovf-chcap"] = xp_case(2049, 3, 1, N2049_ROWS, [], m2, 59, flags=XP_INLINE, CHCAP=1)
+    out["ovf-xa-peer"] = xp_case(2049, 3, 1, N2049_ROWS, [], m2, 60, flags=XP_INLINE, XA_PEER=256 + CH * 4, XI=1024)
+    # MSGCAP = 4 and six local messages: k_pack_all reads at most MSGCAP messages of a tick, so the column passes MSGCAP only
+    # with messages already queued (xn[4] = 2, as k_sync_redeliver leaves them) and four more
+    m4 = [xp_msg(i, i % 2, (i + 1) % 2) for i in range(4)]
+    out["ovf-msgcap"] = xp_case(5, 2, 0, [([0], []), ([], [])], [], m4, 61, MSGCAP=4, xn4=2, RQCAP=4)
+    # ack resolution: log prefixes of 0, 1, 16 and 17 (past TL: none shipped) subjects, to a peer and locally
+    ma = [xp_msg(i, 683 + i % 4, [9, 690][i // 4], kind=2 | KF_RES, tln=[0, 1, 16, 17][i % 4]) for i in range(8)]
+    ma += [xp_msg(8, 684, 10, kind=1, tln=5), xp_msg(9, 685, 691, kind=2, tln=5)]  # no KF_RES: no prefix
+    out["ackres-on"] = xp_case(2049, 3, 1, N2049_ROWS, [], ma, 62, flags=XP_INLINE | XP_ACKRES)
+    out["ackres-off"] = xp_case(2049, 3, 1, N2049_ROWS, [], ma, 62, flags=XP_INLINE)
+    return out
+
+
+def xp_shape(c):
+    """What a case reaches, for tests/test_prim_ref.py: batches of the block scans, chunks copied per block of each peer
+    column (chunk r of a column goes to block r % 16), MW, and each peer region's bytes."""
+    ref = xpack_ref(c)
+    per_block = {q: [sum(1 for r in range(reg["nchunk"]) if r % 16 == x) for x in range(16)]
+                 for q, reg in enumerate(ref["regions"]) if reg}
+    return dict(batches=-(-min(len(c["msgs"]), c["MSGCAP"]) // 256), per_block=per_block, MW=sd_sizes(c["N"])["MW"],
+                bytes={q: reg["bytes"] for q, reg in enumerate(ref["regions"]) if reg}, err=ref["err"],
+                fits={q: reg["fits"] for q, reg in enumerate(ref["regions"]) if reg})
+
+
+# ---- k_unpack_a (with msgs_commit, tick_end and the speculative gate), optionally behind k_inline_in
+XU_END, XU_SPEC, XU_HALTED, XU_ACKRES, XU_INLINE_IN, XU_GOSSIP = 1, 2, 4, 8, 16, 32
+XU_SC = ["nmsg0", "nmsg1", "arena0", "arena1"] + [f"xn{i}" for i in range(8)] + ["err", "halt", "pool_used", "rc_n", "ndl", "ndlw"]
+S16_EVER, USER_SUBJ, ST_DEAD = 1 << 13, 0xFFFFFFFF, 3
+XU_GOSSIP_DEFAULT = dict(SLOTS=128, BCAP=4, LOGW=2, F=8, EXPB=30, gossip_t=3)
+
+
+def rg_entry(g, infp):
+    return g | ((infp & 1023) << 22)
+
+
+def rounds_before(first, c, gossip_t):
+    """Gossip rounds of a member (first round at tick `first`, one every gossip_t ticks) strictly before tick c."""
+    return 0 if first == NEVER or c <= first else -(-(c - first) // gossip_t)
+
+
+def xu_case(q, senders, local=(), k=7, flags=0, gossip=None, **kw):
+    """What rank q receives in one tick. senders: {p: XPACK case of rank p}; the region of p is xpack_ref's, so the
+    unpacker is tested against a known-good packer. local: the messages already queued in mtmp. What the case expects is
+    derived from the senders' messages, not from the regions' bytes: entries = [dict(msg, mask, off, keys, log)]."""
+    c0 = next(iter(senders.values()))
+    N, W = c0["N"], c0["W"]
+    XA = kw.pop("XA_PEER", max(c["XA_PEER"] for c in senders.values()))
+    recv, rcnt, entries = np.full((W, XA), XP_BYTE, np.uint8), np.zeros(W, np.uint64), []
+    for p, c in senders.items():
+        assert c["rank"] == p != q and (c["N"], c["W"]) == (N, W) and c["XA_PEER"] <= XA
+        ref = xpack_ref(c)
+        reg, lo = ref["regions"][q], shard_lo(N, W, p)
+        recv[p][:c["XA_PEER"]] = ref["xa_send"][q]
+        rcnt[p] = ref["xa_scnt"][q]
+        for i, base, mask, _ in reg["entries"]:
+            m = c["msgs"][i]
+            log = c["tlog"][m["src"] - lo][:m["tln"]] if m["kind"] & KF_RES and m["tln"] <= TL else u32([])
+            entries.append(dict(msg=m, mask=mask, off=p * XA + reg["data_off"] + base * CH * 4, keys=xp_payload(c, m)[0], log=log))
+    scnt = np.full(W, 32, np.uint64)
+    scnt[q] = 0
+    case = dict(N=N, W=W, rank=q, k=k, flags=flags | (XU_GOSSIP if gossip is not None else 0), AR=64, XA_PEER=XA, XI=1024,
+                local=[dict(m) for m in local], recv=recv, rcnt=rcnt, scnt=scnt, entries=entries, base=c0["base"],
+                senders=senders, MSGCAP=len(local) + len(entries) + 1, RXCAP=len(entries) + 1, gossip=gossip)
+    case.update(kw)
+    return case
+
+
+def xu_gossip_state(N, seed, **kw):
+    """The small gossip-plane state slot_create and the round replay read: every member's first round tick (some NEVER),
+    ring head and end, log position (0, mid-ring and wrapped ones) and the spreads logged before."""
+    g = dict(XU_GOSSIP_DEFAULT, **kw)
+    rng = np.random.default_rng(seed)
+    first = rng.integers(0, 40, N).astype(np.uint32)
+    first[::5] = NEVER
+    rhead = rng.integers(0, 2**32, N, dtype=np.uint32)
+    rhead[::3] = 0
+    g.update(first=first, rhead=rhead, rtail=rhead.copy(), log_pos=(np.arange(N) % 5).astype(np.uint32),
+             log_spread=rng.integers(3, 6, (N, g["LOGW"])).astype(np.uint32))
+    return g
+
+
+def xu_blocks(case):
+    """The inline blocks [W][XI] of the case's regions: the count word, then the region's head."""
+    XI = case["XI"]
+    blocks = np.full((case["W"], XI), XP_BYTE, np.uint8)
+    for p in range(case["W"]):
+        blocks[p][:8] = np.array([case["rcnt"][p]], np.uint64).view(np.uint8)
+        blocks[p][8:] = case["recv"][p][:XI - 8]
+    return blocks
+
+
+def xu_sizes(case):
+    z, g = sd_sizes(case["N"]), case["gossip"]
+    N, W, CAP, RX = case["N"], case["W"], case["MSGCAP"], case["RXCAP"]
+    core = [("msgs", np.uint32, (CAP, SMW)), ("m_head", np.uint32, (N,)), ("m_next", np.uint32, (CAP,)),
+            ("rx_mask", np.uint64, (RX, z["MW"])), ("rx_off", np.uint64, (RX,)), ("mlog", np.uint32, (CAP, TL)),
+            ("sc", np.uint32, (18,)), ("xa_scnt", np.uint64, (W,)), ("xb_scnt", np.uint64, (W,)), ("xdone", np.uint32, (2 * W,)),
+            ("xa_rcnt", np.uint64, (W,)), ("host", np.uint64, (2 * W,))]
+    if g is not None:
+        S, Q, B, L, F = g["SLOTS"], g["SLOTS"] // 64, g["BCAP"], g["LOGW"], g["F"]
+        core += [("slot_gid", np.uint64, (S,)), ("slot_key", np.uint64, (S,)), ("slot4", np.uint32, (4, S)), ("gudm", np.uint64, (2, Q)),
+                 ("S", np.uint16, (N, S)), ("HB", np.uint64, (N, Q)), ("rg", np.uint32, (N, B)), ("mem8", np.uint32, (8, N)),
+                 ("T", np.uint32, (N, F)), ("log3", np.uint32, (3, N, L)), ("log_tg", np.uint32, (N, L, F))]
+    return core
+
+
+def xu_pack(case):
+    """(params, in, out) of a SWIM_PRIM_XUNPACK call; out is preset to XP_BYTE."""
+    g, fl = case["gossip"], case["flags"]
+    parts = [xu_blocks(case) if fl & XU_INLINE_IN else case["recv"], case["rcnt"], case["scnt"],
+             u32([msg_words(m) for m in case["local"]]).reshape(-1)]
+    if g is not None:
+        parts += [u32(g["first"]), u32(g["rhead"]), u32(g["rtail"]), u32(g["log_pos"]), u32(g["log_spread"])]
+    raw = b"".join(np.ascontiguousarray(a).tobytes() for a in parts)
+    inp = np.frombuffer(raw + b"\0" * (-len(raw) % 8 + 8), np.uint64).copy().view(np.uint8)[:len(raw)]
+    gg = g or dict(SLOTS=0, BCAP=0, LOGW=0, F=0, EXPB=0, gossip_t=0)
+    params = [case["N"], case["W"], case["rank"], case["k"], fl, case["MSGCAP"], case["RXCAP"], case["AR"], case["XA_PEER"],
+              case["XI"], len(case["local"]), gg["SLOTS"], gg["BCAP"], gg["LOGW"], gg["F"], gg["EXPB"], gg["gossip_t"], XP_WORD]
+    nout = sum(np.dtype(dt).itemsize * int(np.prod(sh)) for _, dt, sh in xu_sizes(case))
+    return params, inp, np.full(nout // 8 + 1, XP_WORD64, np.uint64).view(np.uint8)[:nout]
+
+
+def xu_unpack(case, out):
+    r, pos = {}, 0
+    for name, dt, sh in xu_sizes(case):
+        n = np.dtype(dt).itemsize * int(np.prod(sh))
+        r[name] = np.frombuffer(out[pos:pos + n].tobytes(), dt).reshape(sh)
+        pos += n
+    assert pos == len(out)
+    r["sc"] = dict(zip(XU_SC, (int(v) for v in r["sc"])))
+    return r
+
+
+def xu_gate(case):
+    """The speculative gate: some shard has a gossip slot in use or a region past its inline block."""
+    f = 0
+    for p in range(case["W"]):
+        f |= int(case["rcnt"][p]) | int(case["scnt"][p])
+        if int(case["scnt"][p]) & XCNT_MASK > case["XI"] - 8:
+            f |= XFLAG_OVER
+    return bool(f & (XFLAG_GOSSIP | XFLAG_OVER))
+
+
+def xu_region(case, p):
+    """An independent parse of peer p's region, by the layout: (slot records, round records, [(message words, chunk base,
+    mask, log words)], data_off); None if the peer contributes nothing."""
+    MW = sd_sizes(case["N"])["MW"]
+    if p == case["rank"] or int(case["rcnt"][p]) & XCNT_MASK < 32:
+        return None
+    Rg = case["recv"][p]
+    H = np.frombuffer(Rg[:32].tobytes(), np.uint32)
+    nslot, nround, nsync, data_off = (int(H[i]) for i in (0, 1, 2, 4))
+    o = 32
+    ns = np.frombuffer(Rg[o:o + 4 * NSW * nslot].tobytes(), np.uint32).reshape(nslot, NSW)
+    o += 4 * NSW * nslot
+    rr = np.frombuffer(Rg[o:o + 4 * RRW * nround].tobytes(), np.uint32).reshape(nround, RRW)
+    o += 4 * RRW * nround
+    SE, ent = sync_entry_size(MW), []
+    for j in range(nsync):
+        w = np.frombuffer(Rg[o + SE * j:o + SE * (j + 1)].tobytes(), np.uint32)
+        ent.append((w[:SMW], int(w[SMW]), mask_int(w[SMW + 2:SMW + 2 + 2 * MW].view(np.uint64)), w[SMW + 2 + 2 * MW:]))
+    return ns, rr, ent, data_off
+
+
+def xunpack_ref(case):
+    """What k_unpack_a leaves (the arrays of xu_unpack, preset to the sentinel), with the indices the atomics hand out
+    taken in region order: peers ascending, entries in order. Any other order is as valid; xu_props states what does not
+    depend on it."""
+    z, fl = sd_sizes(case["N"]), case["flags"]
+    N, W, CAP, RX, k = case["N"], case["W"], case["MSGCAP"], case["RXCAP"], case["k"]
+    r = {name: np.full(sh, {1: XP_BYTE, 2: 0xA5A5, 4: XP_WORD, 8: XP_WORD64}[np.dtype(dt).itemsize], dt) for name, dt, sh in xu_sizes(case)}
+    b, nloc = k & 1, len(case["local"])
+    sc = dict(zip(XU_SC, [XP_WORD] * 18))
+    sc.update({f"arena{b}": 0, "xn4": nloc, "xn5": 0, "xn6": 0, "err": 0, "halt": 1 if fl & XU_HALTED else 0})
+    r.update(sc=sc, m_head=np.full(N, NEVER, np.uint32), xa_scnt=np.array(case["scnt"], np.uint64),
+             xa_rcnt=np.array(case["rcnt"], np.uint64))
+    if fl & XU_INLINE_IN and not (fl & XU_SPEC and fl & XU_HALTED):
+        r["host"] = np.concatenate([case["scnt"], case["rcnt"]]).astype(np.uint64)
+    elif fl & XU_INLINE_IN:
+        r["xa_rcnt"] = np.full(W, XP_WORD64, np.uint64)
+    g = case["gossip"]
+    if g is not None:
+        r["gudm"][:] = 0
+        r["HB"][:] = 0
+        r["mem8"][0], r["mem8"][1], r["mem8"][7], r["log3"][1] = g["rtail"], 0, g["log_pos"], g["log_spread"]
+    if fl & XU_SPEC and (fl & XU_HALTED or xu_gate(case)):
+        if not fl & XU_HALTED:
+            sc["halt"] = k + 1
+        return r
+    mtmp = [msg_words(m) for m in case["local"]]
+    xn4, xn5 = nloc, 0
+    for p in range(W):
+        reg = xu_region(case, p)
+        if reg is None:
+            continue
+        ns, rr, ent, data_off = reg
+        for rec in ns:
+            gs, origin, kc = int(rec[0]), int(rec[7]), int(rec[4])
+            gid, key = int(rec[1]) | int(rec[2]) << 32, int(rec[5]) | int(rec[6]) << 32
+            r["slot_gid"][gs], r["slot_key"][gs] = gid, key
+            r["slot4"][:, gs] = [int(rec[3]), kc, (kc + g["EXPB"]) & M32, 1]
+            r["gudm"][0][gs >> 6] |= np.uint64(1 << (gs & 63))
+            if int(rec[3]) != USER_SUBJ and (key >> 32) & 3 == ST_DEAD:
+                r["gudm"][1][gs >> 6] |= np.uint64(1 << (gs & 63))
+            r["S"][origin][gs] = S16_EVER | (kc & S16_TICK)
+            r["HB"][origin][gs >> 6] |= np.uint64(1 << (gs & 63))
+            pos = int(r["mem8"][0][origin])
+            r["rg"][origin][pos & (g["BCAP"] - 1)] = rg_entry(gs, rounds_before(int(g["first"][origin]), kc, g["gossip_t"]))
+            r["mem8"][0][origin] = (pos + 1) & M32
+            r["mem8"][1][origin] += 1
+        for rec in rr:
+            m, cnt = int(rec[0]), int(rec[1])
+            lp = int(r["mem8"][7][m])
+            pos = lp % g["LOGW"]
+            r["mem8"][2][m], r["mem8"][3][m], r["mem8"][4][m], r["mem8"][5][m] = 1, cnt, rec[2], rec[3]
+            if lp > 0 and int(r["log3"][1][m][(lp - 1) % g["LOGW"]]) != int(rec[2]):
+                r["mem8"][6][m] = k
+            r["log3"][0][m][pos], r["log3"][1][m][pos], r["log3"][2][m][pos] = k, rec[2], cnt
+            r["T"][m][:cnt] = rec[4:4 + cnt]
+            r["log_tg"][m][pos][:cnt] = rec[4:4 + cnt]
+            r["mem8"][7][m] = lp + 1
+        for mw, base, mask, logw in ent:
+            ri, j = xn5, xn4
+            xn5, xn4 = xn5 + 1, xn4 + 1
+            if ri >= RX or j >= CAP:
+                sc["err"] |= E_XCAP
+                continue
+            m = dict(zip(SM_FIELDS, (int(v) for v in mw)))
+            r["rx_mask"][ri] = [(mask >> (64 * w)) & M64 for w in range(z["MW"])]
+            r["rx_off"][ri] = p * case["XA_PEER"] + data_off + base * CH * 4
+            if fl & XU_ACKRES and m["kind"] & KF_RES and m["tln"] <= TL:
+                r["mlog"][j][:m["tln"]] = logw[:m["tln"]]
+            m.update(payload=PAY_RX | ri, ncand=0)
+            while len(mtmp) < j:
+                mtmp.append(np.zeros(SMW, np.uint32))  # a slot a refused entry took: mtmp as it was (zero here)
+            mtmp.append(msg_words(m))
+    n = min(xn4, CAP)
+    while len(mtmp) < n:
+        mtmp.append(np.zeros(SMW, np.uint32))
+    PIN, PAY, DST, KIND = (SM_FIELDS.index(f) for f in ("pin", "payload", "dst", "kind"))
+    used = 0
+    for i in range(n):
+        r["msgs"][i] = mtmp[i]
+        r["msgs"][i][PIN] = NEVER
+    for i in range(n):
+        if int(r["msgs"][i][KIND]) & KF_DEFER:
+            continue
+        dst = int(r["msgs"][i][DST])
+        old = int(r["m_head"][dst])
+        r["m_head"][dst], r["m_next"][i] = i, old
+        if old != NEVER:
+            for t in (i, old):
+                if int(r["msgs"][t][PAY]) == NEVER and int(r["msgs"][t][PIN]) == NEVER:
+                    if used < case["AR"]:
+                        r["msgs"][t][PIN] = used
+                    else:
+                        sc["err"] |= E_ARENA
+                    used += 1
+    sc.update({f"nmsg{b}": n, f"arena{b}": used, "xn4": xn4, "xn5": xn5, "xn6": 32 * W})
+    if fl & XU_END:
+        sc.update({f"xn{i}": 0 for i in range(8)})
+        sc.update({f"nmsg{b ^ 1}": 0, f"arena{b ^ 1}": 0, "pool_used": 0, "rc_n": 0})
+        if fl & XU_ACKRES:
+            sc.update(ndl=0, ndlw=0)
+        r["xa_scnt"][:], r["xb_scnt"][:], r["xdone"][:] = 0, 0, 0
+    return r
+
+
+def xu_props(case, res, holes=0):
+    """Properties 1-4 of an unpacked tick, none of which depends on the order the atomics hand out indices in; holes: the
+    committed slots that entries refused for want of an rx index took and never wrote (an overflow case only)."""
+    z, N, CAP, nloc = sd_sizes(case["N"]), case["N"], case["MSGCAP"], len(case["local"])
+    b = case["k"] & 1
+    sc, msgs = res["sc"], res["msgs"]
+    F = {f: i for i, f in enumerate(SM_FIELDS)}
+    total = nloc + len(case["entries"])
+    assert sc[f"nmsg{b}"] == min(total, CAP), ("nmsg", sc[f"nmsg{b}"], total, CAP)
+    n = min(total, CAP)
+    # 1. the local messages were queued before the launch and keep their places; the received ones are a multiset
+    for i, m in enumerate(case["local"][:n]):
+        want = msg_words(dict(m, pin=int(msgs[i][F["pin"]])))
+        assert np.array_equal(msgs[i], want), ("local message", i, msgs[i].tolist(), want.tolist())
+    ident = lambda w: tuple(int(v) for j, v in enumerate(w) if SM_FIELDS[j] not in ("payload", "ncand", "pin"))
+    expect = {}
+    for e in case["entries"]:
+        key = ident(msg_words(e["msg"]))
+        assert key not in expect, "the case's entries are distinct"
+        expect[key] = e
+    seen, ris, nhole = set(), set(), 0
+    for i in range(nloc, n):
+        w = msgs[i]
+        if holes and not np.delete(w, F["pin"]).any():
+            nhole += 1
+            continue
+        key = ident(w)
+        assert key in expect and key not in seen, ("message", i, "is a complete one from the input, once", w.tolist())
+        seen.add(key)
+        e, pay = expect[key], int(w[F["payload"]])
+        assert pay & PAY_RX and pay != NEVER and int(w[F["ncand"]]) == 0, ("message", i, "payload PAY_RX | ri, ncand 0", hex(pay))
+        ri = pay & ~PAY_RX
+        assert ri < min(sc["xn5"], case["RXCAP"]) or case["flags"] & XU_END and ri < case["RXCAP"], ("message", i, "ri", ri)
+        assert ri not in ris, ("message", i, "ri", ri, "handed out twice")
+        ris.add(ri)
+        assert mask_int(res["rx_mask"][ri]) == e["mask"], ("message", i, "rx_mask", ri, hex(mask_int(res["rx_mask"][ri])), hex(e["mask"]))
+        assert int(res["rx_off"][ri]) == e["off"], ("message", i, "rx_off", ri, int(res["rx_off"][ri]), e["off"])
+        if case["flags"] & XU_ACKRES:
+            assert np.array_equal(res["mlog"][i][:len(e["log"])], e["log"]), ("message", i, "mlog prefix")
+        # 4. payload closure: baseline + shipped chunks = the sender's row, for every subject
+        nch = bin(e["mask"]).count("1")
+        flat = case["recv"].reshape(-1)[e["off"]:e["off"] + nch * CH * 4]
+        ship = np.frombuffer(flat.tobytes(), np.uint32).reshape(nch, CH)
+        assert np.array_equal(rx_payload(case["base"], e["mask"], ship)[:N], e["keys"][:N]), ("message", i, "payload closure")
+    assert nhole == holes, ("slots taken and never written", nhole, holes)
+    if not holes and total <= CAP:
+        assert len(seen) == len(expect), "every entry of every region is committed"
+    # 2. inbound lists: exactly the non-deferred messages of each member, each list ends
+    by_dst = {}
+    for i in range(n):
+        if not int(msgs[i][F["kind"]]) & KF_DEFER:
+            by_dst.setdefault(int(msgs[i][F["dst"]]), set()).add(i)
+    heads = {int(m): int(res["m_head"][m]) for m in np.flatnonzero(res["m_head"] != NEVER)}
+    assert set(heads) == set(by_dst), ("members with a list", sorted(heads), sorted(by_dst))
+    for dst, want in by_dst.items():
+        got, qi = [], heads[dst]
+        while qi != NEVER and len(got) <= n:
+            assert qi < n, ("m_next link", dst, qi)
+            got.append(qi)
+            qi = int(res["m_next"][qi])
+        assert qi == NEVER and len(got) == len(set(got)) and set(got) == want, ("inbound list of", dst, got, sorted(want))
+    # 3. pins: a live-row payload of a receiver with two messages or more; at most two live rows per receiver in the cases,
+    # so only the second arrival's thread pins and no arena row is lost to a race (pin_msg, dev_util.h)
+    pins = []
+    for i in range(n):
+        w = msgs[i]
+        listed = not int(w[F["kind"]]) & KF_DEFER
+        must = listed and int(w[F["payload"]]) == NEVER and len(by_dst[int(w[F["dst"]])]) >= 2
+        assert (int(w[F["pin"]]) != NEVER) == must, ("pin of message", i, int(w[F["pin"]]), must)
+        if must:
+            pins.append(int(w[F["pin"]]))
+    assert len(set(pins)) == len(pins) and all(p < sc[f"arena{b}"] for p in pins), ("pins", pins, sc[f"arena{b}"])
+    assert sc[f"arena{b}"] == len(pins), ("arena_used", sc[f"arena{b}"], len(pins))
+
+def _sender(N, W, p, dsts, seed, n_rows=4, **kw):
+    """An XPACK case of rank p whose message i goes from its row i % n_rows to dsts[i]; rows 1 and 3 are dirty."""
+    lo = shard_lo(N, W, p)
+    nch = sd_sizes(N)["NCHUNK"]
+    rows = [([], []), ([0], []), ([], [nch - 1]), ([nch - 1], [])][:n_rows]
+    msgs = [xp_msg(i, lo + i % n_rows, d, **(kw.get("msg_kw", {}).get(i, {}))) for i, d in enumerate(dsts)]
+    return xp_case(N, W, p, rows, [], msgs, seed, **{k_: v for k_, v in kw.items() if k_ != "msg_kw"})
+
+
+def xunpack_cases():
+    """{name: case}: the regions xpack_ref produces for the XPACK cases as a receiving rank sees them (W = 2, 3 and 8),
+    two peers with 300 entries each on top of queued local messages, the pin paths, the region edges, and the gate,
+    end-of-tick, overflow and inline variants."""
+    xp = xpack_cases()
+    g2049 = xu_gossip_state(2049, 81)
+    g2049["log_spread"][683][(3 - 1) % 2], g2049["log_spread"][684][(4 - 1) % 2] = 3, 9  # the rounds' spreads are 3, 4, 5:
+    # member 683 (log_pos 3) logged the same spread before, 684 (log_pos 4) another one, 1365 (log_pos 0) none
+    out = {"n5-w2>1": xu_case(1, {0: xp["n5-w2"]}),
+           "n2049>0": xu_case(0, {1: xp["n2049-w3-r1"]}, gossip=g2049),
+           "n2049>2-end": xu_case(2, {1: xp["n2049-w3-r1"]}, gossip=g2049, flags=XU_END, k=8),
+           "n2049>2-end-ackres": xu_case(2, {1: xp["n2049-w3-r1"]}, gossip=g2049, flags=XU_END | XU_ACKRES),
+           "n4100>1": xu_case(1, {0: xp["n4100-batches"]}),
+           "ackres>0": xu_case(0, {1: xp["ackres-on"]}, flags=XU_ACKRES)}
+    for q in (0, 4, 5, 7):
+        out[f"n131073>{q}"] = xu_case(q, {3: xp["n131073-w8-r3"]})
+    # two peers, 300 entries each, 20 local messages already queued: 96 blocks contend on xn[4] and xn[5]
+    two = {p: _sender(2049, 3, p, [683 + (7 * i + p) % 683 for i in range(300)], 90 + p) for p in (0, 2)}
+    loc = [xp_msg(5000 + i, 683 + i, 900 + i) for i in range(20)]
+    out["two-peers-300"] = xu_case(1, two, local=loc)
+    # overflows of the same tick: MSGCAP less the local messages, then RXCAP, smaller than the entries received
+    out["ovf-msgcap"] = xu_case(1, two, local=loc, MSGCAP=520)
+    out["ovf-rxcap"] = xu_case(1, two, local=loc, RXCAP=500)
+    # pins: receiver 700 gets a local live-row SYNC and a received one; 701 two received; 702 a local arena payload and
+    # a received one; 703 a local live row and a delayed received one; 704 two local live rows; 705 one; 700 also a
+    # delayed local live row, which is in no list
+    snd = _sender(2049, 3, 0, [700, 701, 701, 702, 703], 95, msg_kw={4: dict(kind=1 | KF_DEFER)})
+    loc = [xp_msg(6000, 690, 700), xp_msg(6001, 691, 702, payload=3), xp_msg(6002, 692, 703), xp_msg(6003, 693, 704),
+           xp_msg(6004, 694, 704, kind=2), xp_msg(6005, 695, 705), xp_msg(6006, 696, 700, kind=1 | KF_DEFER)]
+    out["pins"] = xu_case(1, {0: snd}, local=loc)
+    # region edges: a peer whose count is below 32 contributes nothing, the own region is ignored even if it holds bytes
+    e = xu_case(0, {1: xp["n2049-w3-r1"]}, gossip=g2049)
+    rng = np.random.default_rng(96)
+    e["recv"][0], e["recv"][2] = rng.integers(0, 256, e["XA_PEER"], dtype=np.uint8), rng.integers(0, 256, e["XA_PEER"], dtype=np.uint8)
+    e["rcnt"][0], e["rcnt"][2] = 4096, 24
+    out["edges"] = e
+    # W = 8 with the gossip plane: every peer of rank 2 created two gossips (one origin both) and ran one round
+    send = {}
+    for p in (0, 1, 3, 4, 5, 6, 7):
+        lo = shard_lo(64, 8, p)
+        ns, rr = xp_records(64, [16 * p + 1, 16 * p + 9], [p % 9], 100 + p, origins=[lo + 1, lo + 1], members=[lo + 2])
+        send[p] = xp_case(64, 8, p, [([], [])], [], [], 100 + p, ns_rec=ns, rr_rec=rr, xn0=2, xn1=1, used=2)
+    out["gossip-w8"] = xu_case(2, send, gossip=xu_gossip_state(64, 82))
+    # the speculative gate (k_unpack_a): flags or an oversized sent region stop the launch, nothing else does
+    plain = lambda **kw: xu_case(1, {0: xp["n5-w2"]}, **kw)
+    out["spec-runs"] = plain(flags=XU_SPEC)
+    out["spec-halted"] = plain(flags=XU_SPEC | XU_HALTED)
+    out["spec-gossip-received"] = xu_case(0, {1: xp["n2049-w3-r1"]}, gossip=g2049, flags=XU_SPEC)
+    for name, arr, p, v in (("spec-over-received", "rcnt", 0, XFLAG_OVER), ("spec-gossip-sent", "scnt", 0, XFLAG_GOSSIP),
+                            ("spec-over-sent", "scnt", 1, XFLAG_OVER)):
+        c = plain(flags=XU_SPEC)
+        c[arr][p] = int(c[arr][p]) | v
+        out[name] = c
+    c = plain(flags=XU_SPEC)
+    c["scnt"][0] = c["XI"]  # past the inline block, without the flag
+    out["spec-sent-past-inline"] = c
+    c = plain(flags=XU_SPEC)
+    c["scnt"][0] = c["XI"] - 8  # exactly the inline block: runs
+    out["spec-sent-at-inline"] = c
+    # behind k_inline_in: a region that is exactly the inline block, one with a partial chunk, and a halted launch
+    out["inline-in-256"] = xu_case(1, {0: xp["inl-xi264"]}, flags=XU_INLINE_IN, XI=264)
+    out["inline-in-chunk"] = xu_case(1, {0: xp["n5-w2"]}, flags=XU_INLINE_IN | XU_SPEC, XI=16384)
+    out["inline-in-halted"] = xu_case(1, {0: xp["inl-xi264"]}, flags=XU_INLINE_IN | XU_SPEC | XU_HALTED, XI=264)
+    return out
+
+
+# ---- k_pack_b and k_inline_in
+PACKB_NDS = [0, 1, 16384, 16385]  # around the 64 x 256 grid stride
+
+
+def pack_b_ref(W, rank, DCAP, xd_n, XB, xd):
+    """(xb_send uint8[W][XB], xb_scnt uint64[W], err) in buffers preset to XP_BYTE: header {nd, 0, 0, 0}, then the
+    records; nd clamps to DCAP; records that pass XB_PEER raise E_XCAP and ship a header only."""
+    send, scnt, err = np.full((W, XB), XP_BYTE, np.uint8), np.full(W, XP_WORD64, np.uint64), 0
+    nd = min(xd_n, DCAP)
+    if 16 + 8 * nd > XB:
+        err, nd = E_XCAP, 0
+    for q in range(W):
+        if q != rank:
+            send[q][:16] = u32([nd, 0, 0, 0]).view(np.uint8)
+            send[q][16:16 + 8 * nd] = np.asarray(xd[:nd], np.uint64).view(np.uint8)
+            scnt[q] = 16 + 8 * nd
+    return send, scnt, err
+
+
+def inline_in_ref(W, XI, cap, irecv, scnt, halted):
+    """(recv uint8[W][cap], rcnt uint64[W], host uint64[2 W]) in buffers preset to XP_BYTE."""
+    recv, rcnt, host = np.full((W, cap), XP_BYTE, np.uint8), np.full(W, XP_WORD64, np.uint64), np.full(2 * W, XP_WORD64, np.uint64)
+    if not halted:
+        for p in range(W):
+            w = int(np.frombuffer(irecv[p][:8].tobytes(), np.uint64)[0])
+            n = min(w & XCNT_MASK, XI - 8) // 8 * 8
+            recv[p][:n] = irecv[p][8:8 + n]
+            rcnt[p], host[p], host[W + p] = w, scnt[p], w
+    return recv, rcnt, host

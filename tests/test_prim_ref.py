@@ -490,3 +490,239 @@ def test_mask_and_pin_cases():
                     assert "pin" not in hows
                 if variant.startswith("dirty"):
                     assert [w for r in range(8) for w in range(3) if case["dirty"][r][w]] == [z["MW"] - 1]
+
+
+# ------------------------------------------------------------------------------------- row-shard exchange codec
+import re
+import struct
+from pathlib import Path
+
+CSRC = Path(__file__).resolve().parent.parent / "scalecube-cluster_amd" / "csrc"
+XP = R.xpack_cases()
+XU = R.xunpack_cases()
+
+
+def test_sync_entry_size_against_engine_h():
+    """The references' SyncMsg is engine.h's, field for field, and an entry is SyncMsg + 8 + 8 MW + 4 TL bytes: a change
+    of the struct breaks this test, not the meaning of the others."""
+    text = (CSRC / "engine.h").read_text()
+    body = re.search(r"struct SyncMsg \{(.*?)\n\};", text, re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    fields = [f.strip() for decl in re.findall(r"uint32_t ([^;]+);", body) for f in decl.split(",")]
+    assert tuple(fields) == R.SM_FIELDS and 4 * R.SMW == 52
+    assert re.search(r"sync_entry_size\(uint32_t MW\) \{ return sizeof\(SyncMsg\) \+ 8 \+ 8ull \* MW \+ 4ull \* TL; \}", text)
+    assert re.search(r"constexpr uint32_t TL = 16;", text) and R.TL == 16
+    assert re.search(r"RRW = 12;", text) and re.search(r"NSW = 8;", text) and (R.NSW, R.RRW) == (8, 12)
+    assert [R.sync_entry_size(MW) for MW in (1, 2, 3)] == [132, 140, 148]
+    for name, v in (("XFLAG_GOSSIP", 62), ("XFLAG_OVER", 61)):
+        assert re.search(rf"{name} = 1ull << {v}", text) and getattr(R, name) == 1 << v
+    assert re.search(r"E_MSGS = 32,", text) and re.search(r"E_XCAP = 1u << 17", text) and re.search(r"PAY_RX = 0x40000000u", text)
+
+
+def test_shard_routing_refs_agree_with_shard_range():
+    from swimhip.shard import shard_range
+    for n, w in [(64, 2), (300, 3), (100_000, 8), (50, 7), (131073, 8), (5, 2), (5, 3), (2049, 3), (4100, 2)]:
+        for r in range(w):
+            lo, hi = shard_range(n, w, r)
+            assert (R.shard_lo(n, w, r), R.shard_lo(n, w, r + 1)) == (lo, hi)
+            for m in {lo, hi - 1, (lo + hi) // 2} if hi > lo else ():
+                assert R.shard_of(n, w, m) == r, (n, w, m)
+
+
+def naive_region(buf, MW):
+    """A header walk with struct.unpack, nothing shared with xpack_ref: (header, slot records, round records, entries =
+    [(13 message words, base, pad, mask words, 16 log words)], the byte where the entries end)."""
+    H = struct.unpack_from("<8I", buf, 0)
+    o = 32
+    ns = [struct.unpack_from("<8I", buf, o + 32 * i) for i in range(H[0])]
+    o += 32 * H[0]
+    rr = [struct.unpack_from("<12I", buf, o + 48 * i) for i in range(H[1])]
+    o += 48 * H[1]
+    ent = []
+    for _ in range(H[2]):
+        msg = struct.unpack_from("<13I", buf, o)
+        base, pad = struct.unpack_from("<2I", buf, o + 52)
+        mask = struct.unpack_from(f"<{MW}Q", buf, o + 60)
+        log = struct.unpack_from("<16I", buf, o + 60 + 8 * MW)
+        ent.append((msg, base, pad, mask, log))
+        o += 60 + 8 * MW + 64
+    return H, ns, rr, ent, o
+
+
+@pytest.mark.parametrize("name", list(XP))
+def test_xpack_ref_parses_back(name):
+    c = XP[name]
+    ref, z = R.xpack_ref(c), R.sd_sizes(c["N"])
+    N, W, rank, MW = c["N"], c["W"], c["rank"], z["MW"]
+    lo = R.shard_lo(N, W, rank)
+    if c["flags"] & R.XP_HALTED:
+        assert all((ref[f].view(np.uint8) == R.XP_BYTE).all() for f in ("xa_send", "xa_scnt", "xi_send", "mtmp", "mlog"))
+        return
+    sent = [m for m in c["msgs"][:c["MSGCAP"]]]
+    for q in range(W):
+        if q == rank:
+            assert (ref["xa_send"][q] == R.XP_BYTE).all()
+            continue
+        buf = ref["xa_send"][q].tobytes()
+        H, ns, rr, ent, end = naive_region(buf, MW)
+        bytes_ = int(ref["xa_scnt"][q]) & R.XCNT_MASK
+        assert bool(int(ref["xa_scnt"][q]) & R.XFLAG_GOSSIP) == (c["used"] > 0)
+        want = [m for m in sent if lo_hi(N, W, q)[0] <= m["dst"] < lo_hi(N, W, q)[1]]
+        if not ref["regions"][q]["fits"]:
+            assert H == (0, 0, 0, 0, 256, 0, 0, 0) and bytes_ == 32 and set(buf[32:]) == {R.XP_BYTE}
+            continue
+        assert H[5:] == (0, 0, 0) and H[4] % 256 == 0 and end <= H[4] < end + 256 and bytes_ == H[4] + H[3] * R.CH * 4 <= c["XA_PEER"]
+        assert [list(r) for r in ns] == np.asarray(c["ns_rec"])[:H[0]].tolist() and H[0] == min(c["xn0"], c["NSCAP"])
+        assert [list(r) for r in rr] == np.asarray(c["rr_rec"])[:H[1]].tolist() and H[1] == min(c["xn1"], c["RRCAP"])
+        assert len(ent) == len(want)
+        nxt = 0
+        for (msg, base, pad, mask, log), m in zip(ent, want):
+            assert list(msg) == [m[f] for f in R.SM_FIELDS] and pad == 0 and base == nxt
+            row = c["rows"][m["src"] - lo] if m["payload"] == R.NEVER else c["arena"][m["payload"]]
+            dirty = c["rdirty"][m["src"] - lo] if m["payload"] == R.NEVER else c["arena_dirty"][m["payload"]]
+            assert R.mask_int(mask) == dirty
+            nlog = m["tln"] if c["flags"] & R.XP_ACKRES and m["kind"] & R.KF_RES and m["tln"] <= R.TL else 0
+            assert list(log[:nlog]) == c["tlog"][m["src"] - lo][:nlog].tolist() and set(log[nlog:]) <= {R.XP_WORD}
+            for ch in range(z["NCHUNK"]):
+                if (dirty >> ch) & 1:
+                    n = min(R.CH, z["NS"] - ch * R.CH)
+                    got = struct.unpack_from(f"<{R.CH}I", buf, H[4] + nxt * R.CH * 4)
+                    assert list(got[:n]) == row[ch * R.CH:ch * R.CH + n].tolist() and set(got[n:]) <= {R.XP_WORD}
+                    nxt += 1
+        assert nxt == H[3] and set(buf[end:H[4]]) <= {R.XP_BYTE} and set(buf[bytes_:]) <= {R.XP_BYTE}
+
+
+def lo_hi(N, W, q):
+    return q * N // W, (q + 1) * N // W
+
+
+def test_xpack_cases_reach_their_edges():
+    sh = {n: R.xp_shape(c) for n, c in XP.items()}
+    z = lambda n: R.sd_sizes(XP[n]["N"])
+    assert z("n5-w2")["NS"] == 8 and z("n5-w2")["NCHUNK"] == 1 and sh["n5-w2"]["bytes"] == {1: 256 + 8192}
+    assert [R.shard_of(5, 2, m["dst"]) for m in XP["n5-w2"]["msgs"]] == [0, 1, 0]
+    assert z("n2049-w3-r1")["NS"] == 2056 and z("n2049-w3-r1")["NCHUNK"] == 2
+    c = XP["n2049-w3-r1"]
+    masks = {R.xp_payload(c, m)[1] for m in c["msgs"]}
+    assert masks == {0, 1, 2, 3} and {m["payload"] for m in c["msgs"]} == {R.NEVER, 0, 1}
+    assert [int(r[1]) for r in c["rr_rec"]] == [0, 1, 8] and len(c["ns_rec"]) == 3
+    c = XP["n4100-batches"]
+    dests = [R.shard_of(4100, 2, m["dst"]) for m in c["msgs"]]
+    assert dests.count(1) == 600 and dests.count(0) == 300 and sh["n4100-batches"]["batches"] >= 3 and z("n4100-batches")["NCHUNK"] == 3
+    assert all(dests[i] == 1 and R.xp_payload(c, c["msgs"][i])[1] for i in (255, 256, 257, 511, 512))
+    assert sum(sh["n4100-batches"]["per_block"][1]) > 16 and min(sh["n4100-batches"]["per_block"][1]) >= 1
+    c = XP["n131073-w8-r3"]
+    assert sh["n131073-w8-r3"]["MW"] == 2 and z("n131073-w8-r3")["NCHUNK"] == 65 and len(c["rows"]) == 4
+    assert {ch for m in c["msgs"] for ch in R.mask_chunks(R.xp_payload(c, m)[1])} == {0, 63, 64}
+    assert sh["n131073-w8-r3"]["bytes"][5] == 256 and set(sh["n131073-w8-r3"]["bytes"]) == {0, 1, 2, 4, 5, 6, 7}
+    assert all(v > 256 for q, v in sh["n131073-w8-r3"]["bytes"].items() if q != 5)
+    for XI, rel in ((272, -16), (264, -8), (256, 0), (248, 8)):
+        assert sh[f"inl-xi{XI}"]["bytes"] == {1: 256} and 256 - XI == rel
+    assert XP["inl-xi64"]["XI"] == 64 and not XP["inl-off"]["flags"] & R.XP_INLINE
+    c = XP["inl-one-over"]
+    assert sh["inl-one-over"]["bytes"] == {1: c["XI"] - 8, 2: c["XI"] - 8 + 8192}
+    for n, q in (("ovf-rqcap", 0), ("ovf-chcap", 0), ("ovf-xa-peer", 0)):
+        assert sh[n]["fits"] == {0: False, 2: True} and sh[n]["err"] == R.E_XCAP, n
+    c = XP["ovf-rqcap"]
+    assert c["RQCAP"] == 2 and sum(R.shard_of(2049, 3, m["dst"]) == 0 for m in c["msgs"]) == 3
+    c = XP["ovf-chcap"]
+    assert c["CHCAP"] == 1 and bin(R.xp_payload(c, c["msgs"][0])[1]).count("1") == 2
+    c = XP["ovf-xa-peer"]
+    assert c["XA_PEER"] == 256 + 2 * 8192 - 8192 and sh["ovf-xa-peer"]["bytes"][2] == c["XA_PEER"]
+    c = XP["ovf-msgcap"]
+    assert c["MSGCAP"] == 4 and c["xn4"] + sum(R.shard_of(5, 2, m["dst"]) == 0 for m in c["msgs"]) == 6 and sh["ovf-msgcap"]["err"] == R.E_MSGS
+    c = XP["ackres-on"]
+    assert sorted({m["tln"] for m in c["msgs"] if m["kind"] & R.KF_RES}) == [0, 1, 16, 17]
+    assert XP["ackres-off"]["msgs"] == c["msgs"] and not XP["ackres-off"]["flags"] & R.XP_ACKRES
+
+
+def test_xpack_masks_are_consistent_with_the_rows():
+    """A mask bit is set if the chunk differs from the baseline (and on some equal chunks, which is allowed); a clear bit
+    means equal: what the payload closure rests on."""
+    extra = 0
+    for c in XP.values():
+        z = R.sd_sizes(c["N"])
+        assert not c["base"][c["N"]:].any()
+        for row, mask in list(zip(c["rows"], c["rdirty"])) + list(zip(c["arena"], c["arena_dirty"])):
+            for ch in range(z["NCHUNK"]):
+                differs = not np.array_equal(row[ch * R.CH:(ch + 1) * R.CH], c["base"][ch * R.CH:(ch + 1) * R.CH])
+                assert not differs or (mask >> ch) & 1
+                extra += (mask >> ch) & 1 and not differs
+            assert mask >> z["NCHUNK"] == 0
+    assert extra > 0
+
+
+@pytest.mark.parametrize("name", list(XU))
+def test_xunpack_ref_round_trip(name):
+    """xunpack_ref(xpack_ref(case)) satisfies the order-free properties (messages, lists, pins, payload closure)."""
+    c = XU[name]
+    r = R.xunpack_ref(c)
+    b = c["k"] & 1
+    if c["flags"] & R.XU_SPEC and (c["flags"] & R.XU_HALTED or R.xu_gate(c)):
+        assert r["sc"][f"nmsg{b}"] == R.XP_WORD and (r["msgs"] == R.XP_WORD).all() and (r["m_head"] == R.NEVER).all()
+        assert r["sc"]["halt"] == (1 if c["flags"] & R.XU_HALTED else c["k"] + 1)
+        return
+    R.xu_props(c, r, holes={"ovf-rxcap": 100}.get(name, 0))
+    # the reference's own parse agrees with what the case expects, entry for entry
+    ent = [e for p in range(c["W"]) for e in (R.xu_region(c, p) or ((), (), (), 0))[2]]
+    assert len(ent) == len(c["entries"])
+    for (mw, base, mask, logw), e in zip(ent, c["entries"]):
+        assert mw.tolist() == R.msg_words(e["msg"]).tolist() and mask == e["mask"]
+
+
+def test_xunpack_cases_reach_their_edges():
+    assert {XU[n]["W"] for n in XU} == {2, 3, 8}
+    c = XU["two-peers-300"]
+    assert len(c["senders"]) == 2 and all(len(s["msgs"]) == 300 for s in c["senders"].values()) and len(c["local"]) == 20
+    assert len(c["entries"]) == 600 and XU["ovf-msgcap"]["MSGCAP"] < 620 <= XU["ovf-msgcap"]["RXCAP"] + 20
+    assert XU["ovf-rxcap"]["RXCAP"] < 600 and XU["ovf-rxcap"]["MSGCAP"] >= 620
+    r = R.xunpack_ref(XU["pins"])
+    F = {f: i for i, f in enumerate(R.SM_FIELDS)}
+    pinned = {int(w[F["seq"]]) for w in r["msgs"][:r["sc"]["nmsg1"]] if int(w[F["pin"]]) != R.NEVER}
+    assert pinned == {1000 + 6000, 1000 + 6003, 1000 + 6004} and r["sc"]["arena1"] == 3
+    per_dst = {}
+    for w in r["msgs"][:r["sc"]["nmsg1"]]:
+        if int(w[F["payload"]]) == R.NEVER and not int(w[F["kind"]]) & R.KF_DEFER:
+            per_dst[int(w[F["dst"]])] = per_dst.get(int(w[F["dst"]]), 0) + 1
+    assert max(per_dst.values()) <= 2, "at most two live rows per receiver: no arena row is lost to a pin race"
+    e = XU["edges"]
+    assert int(e["rcnt"][2]) == 24 and int(e["rcnt"][0]) >= 32 and e["rank"] == 0
+    g = XU["gossip-w8"]
+    origins = [int(r_[7]) for s in g["senders"].values() for r_ in s["ns_rec"]]
+    assert len(origins) == 14 and len(set(origins)) == 7, "two creations per origin"
+    rr = XU["n2049>0"]["senders"][1]["rr_rec"]
+    st = XU["n2049>0"]["gossip"]
+    changed = [int(st["log_pos"][int(r_[0])]) > 0 and int(st["log_spread"][int(r_[0])][(int(st["log_pos"][int(r_[0])]) - 1) % 2]) != int(r_[2]) for r_ in rr]
+    assert changed == [False, True, False] and [int(st["log_pos"][int(r_[0])]) for r_ in rr] == [3, 4, 0]
+    assert R.xu_gate(XU["spec-sent-past-inline"]) and not R.xu_gate(XU["spec-sent-at-inline"]) and not R.xu_gate(XU["spec-runs"])
+    assert XU["inline-in-256"]["XI"] - 8 == 256 == int(XU["inline-in-256"]["rcnt"][0]) & R.XCNT_MASK
+
+
+def test_pack_b_and_inline_in_refs():
+    xd = np.arange(100, dtype=np.uint64) + np.uint64(1 << 40)
+    send, scnt, err = R.pack_b_ref(3, 1, 16, 40, 16 + 8 * 16, xd)
+    assert err == 0 and scnt.tolist() == [144, R.XP_WORD64, 144] and struct.unpack_from("<4I", send[0].tobytes()) == (16, 0, 0, 0)
+    assert struct.unpack_from("<16Q", send[2].tobytes(), 16) == tuple(int(v) for v in xd[:16]) and (send[1] == R.XP_BYTE).all()
+    send, scnt, err = R.pack_b_ref(3, 1, 16, 16, 16 + 8 * 15, xd)
+    assert err == R.E_XCAP and scnt[0] == 16 and (send[0][16:] == R.XP_BYTE).all()
+    irecv = np.zeros((2, 64), np.uint8)
+    irecv[:, 8:] = np.arange(56, dtype=np.uint8)
+    irecv[0][:8] = np.array([24 | R.XFLAG_OVER], np.uint64).view(np.uint8)
+    irecv[1][:8] = np.array([4096], np.uint64).view(np.uint8)
+    recv, rcnt, host = R.inline_in_ref(2, 64, 128, irecv, np.array([7, 9], np.uint64), False)
+    assert recv[0][:24].tolist() == list(range(24)) and (recv[0][24:] == R.XP_BYTE).all()
+    assert recv[1][:56].tolist() == list(range(56)) and (recv[1][56:] == R.XP_BYTE).all()
+    assert rcnt.tolist() == [24 | R.XFLAG_OVER, 4096] and host.tolist() == [7, 9, 24 | R.XFLAG_OVER, 4096]
+
+
+def test_exchange_calls_are_well_formed():
+    """The buffers handed to the library: 8-byte aligned, the output preset to the sentinel and of the size the parts add
+    up to (xp_unpack / xu_unpack consume it exactly)."""
+    for c in XP.values():
+        params, inp, out = R.xp_pack(c)
+        assert len(params) == 22 and inp.ctypes.data % 8 == 0 and out.ctypes.data % 8 == 0 and (out == R.XP_BYTE).all()
+        assert R.xp_unpack(c, out)["err"] == R.XP_WORD
+    for c in XU.values():
+        params, inp, out = R.xu_pack(c)
+        assert len(params) == 18 and inp.ctypes.data % 8 == 0 and out.ctypes.data % 8 == 0 and (out == R.XP_BYTE).all()
+        assert R.xu_unpack(c, out)["sc"]["err"] == R.XP_WORD
