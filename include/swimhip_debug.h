@@ -237,7 +237,45 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
  *            inside it, base + popcount(mask) <= nchunk chunks inside it, mask bits past NCHUNK, src / dst / origins / round
  *            members / targets < N, slot ids < SLOTS, cnt <= F; an inline block whose region is longer than it (the engine
  *            fetches the rest first) unless the gate stops the launch; an mtmp entry with src or dst >= N; rtail - rhead >
- *            BCAP; sizes out of the ranges above */
+ *            BCAP; sizes out of the ranges above
+ *
+ * The gossip data plane's per-tick kernels (gossip.hip): the engine's own launchers, unchanged and in their
+ * own grids, for one tick k on a caller-built holder state, on a zeroed Dev that holds only what their kernels read and a
+ * device copy of it (Dev::self). Scope: one GPU (W = XW = 1, lo = 0, hi = N); no link delays (dly_on = 0: the k_gossip_due*
+ * kernels are not launched); exp = 0, dbg_send = null, fastp4 = 0; one settings epoch (ep_from[0] = 0, the others NEVER) and
+ * no per-link setting (link_n = 0). Every array of `in` and `out` starts 8-byte aligned (its bytes are rounded up to a
+ * multiple of 8); `out` is in/out throughout: the caller presets every word, so what a kernel did not write is seen.
+ *
+ * GOSSIP     launch_gossip_send, then with GS_APPLY launch_gossip_apply. QW = SLOTS / 64, NS = N rounded up to 8.
+ *            params (27): N (1..4096); F (1..8); SLOTS (a multiple of 64, 64..2^18, N * SLOTS <= 2^21); BCAP (a power of two
+ *              <= 16384, N * BCAP <= 2^22); LOGW (a power of two <= 256); lat (<= 2^16); gossip_t (1..2^16); EXPB (<= 2^20); k
+ *              (the tick, 1 .. 2^30 - 1); seed_lo, seed_hi; rr_atomic; cev_cap (<= 6, the cache's CEV); CRCAP (1..4096, CRCAP *
+ *              QW <= 2^22); RPCAP, SLOWCAP (1..2^20); RCAP (1..2^22); HCAP (a power of two <= 2^16); sort_cap (a power of two in
+ *              2..4096); rank (< 64) and SPR (>= 1: k_gossip_free returns the slots g with g / SPR == rank); flags (SWIM_PRIM_GS_*);
+ *              cw, cb, cx (the LDS row chunks in 8-byte words of k_round_apply_w (its row limit), k_round_apply_b and k_rx_build;
+ *              0: the engine's own min(1024 | 4096 | 8192, QW); at most those, the 64 KB of LDS a workgroup has); ep_loss
+ *              (<= 100), ep_part (0 / 1) of the one epoch
+ *            flags: GS_APPLY also launch_gossip_apply (rowk is read); GS_EM the emulator counters exist (Dev::em: the exact
+ *              per-send path of k_gossip_send and deliver_one); GS_FB the fallback counters exist (Dev::fb)
+ *            in  slot_gid u64[SLOTS]; slot_key u64[SLOTS]; slot_subj, slot_ctick [SLOTS] each; firstGossip, tround, tcnt,
+ *                tspread, tperiod, spchg, log_pos [N] each; T[N][F]; log_tick, log_spread, log_cnt [N][LOGW] each;
+ *                log_tg[N][LOGW][F]; ep_group[N]; leaving[N]; with GS_APPLY rowk[N][NS]
+ *            out u64: GU, DM [QW] each; HB, WB [N][QW] each; RX[CRCAP][QW]; rp[RPCAP]; slow[SLOWCAP]; hist[HCAP][11];
+ *                rc_raw[RCAP]; rc_key[RCAP]; ctr[C_G] (out only); em[2 N]; fb[16] (both unchanged without their flag);
+ *                then S u16[N][SLOTS]; then u32: rg[N][BCAP]; [N] each: dead_tick, rhead, rtail, rwin, rseen, held, rsend,
+ *                rwnew, rt0, tin_cnt as launch_gossip_send left it (out only: k_gossip_apply clears it), tin_cnt, tin_fill (out
+ *                only: both start a tick at 0), tin_off, dead_rx, rc_ndrop, rwl, tlist, ap_list, rc_off, rc_cnt (out only),
+ *                sg_list; [SLOTS] each: slot_exp, slot_used, fexp, free_list; agroup[QW]; [N][F] each: tin, tcontact, cin,
+ *                crow; cev[N][F][22]; rxl[CRCAP][3]; rc_slot[RCAP]; u32[16] = nagroup[2], nrwl, ntl, nrx, rp_n, slow_n, rc_n (must
+ *                start at 0), nap, nsg, nfexp, free_top, hist_n, ncfl, xd_n, 0; err[8] (out only)
+ *            The kernels' own capacity paths are no validation and reach the kernels: E_RING (ring writes are masked),
+ *            E_CONTACTS (rp / slow writes are guarded by RPCAP / SLOWCAP), E_RECEIPTS (rc_raw writes by RCAP), E_SLIFE.
+ *            EINVAL before any launch: a T entry below tcnt or a log target below log_cnt that is >= N; tcnt or log_cnt > F; a
+ *            ring entry of [rhead, rtail) whose slot is >= SLOTS; rtail - rhead > BCAP; rwin or rseen outside [rhead, rtail]
+ *            (positions are absolute and wrap: compared by differences); a slot_subj that is neither USER_SUBJ nor < N;
+ *            free_top < 0 or free_top + popcount(GU) > SLOTS (the free list holds SLOTS entries); rc_n != 0; in / out of the
+ *            wrong length (an ep_group of the wrong length is one); sizes, capacities or chunk overrides out of the ranges
+ *            above; k = 0. (SLOTS is a multiple of 64, so GU / DM / HB / WB have no bit past SLOTS.) */
 #define SWIM_PRIM_SCAN 0u
 #define SWIM_PRIM_SEG_SORT 1u
 #define SWIM_PRIM_ROUTING 2u
@@ -251,6 +289,10 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
 #define SWIM_PRIM_PACK_B 10u
 #define SWIM_PRIM_INLINE_IN 11u
 #define SWIM_PRIM_XUNPACK 12u
+#define SWIM_PRIM_GOSSIP 13u
+#define SWIM_PRIM_GS_APPLY 1u
+#define SWIM_PRIM_GS_EM 2u
+#define SWIM_PRIM_GS_FB 4u
 #define SWIM_PRIM_XP_ACKRES 1u
 #define SWIM_PRIM_XP_INLINE 2u
 #define SWIM_PRIM_XP_SPEC 4u

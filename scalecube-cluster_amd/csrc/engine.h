@@ -581,7 +581,14 @@ struct CensusOut {
 void launch_census(const Dev& d, const uint8_t* sel, uint32_t now, const CensusOut& o, void* stream);
 // launchers one kernel file calls in another
 static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
-void launch_gossip_send(const Dev& d, uint32_t k, hipStream_t st, const TickEvents* prof);  // gossip.hip
+// the LDS row chunks of launch_gossip_send's staged kernels, in 8-byte words (0: the engine's own): cw k_round_apply_w's
+// row limit, cb k_round_apply_b's chunk, cx k_rx_build's chunk. The engine passes none; the known-answer tests set small
+// ones, so the multi-chunk paths exist at small slot tables (swim_debug_prim_eval, SWIM_PRIM_GOSSIP)
+struct GossipChunks {
+  uint32_t cw, cb, cx;
+};
+void launch_gossip_send(const Dev& d, uint32_t k, hipStream_t st, const TickEvents* prof,
+                        const GossipChunks* chunks = nullptr);  // gossip.hip
 void launch_gossip_apply(const Dev& d, uint32_t k, hipStream_t st);
 void launch_unpack_b(const Dev& d, uint32_t k, hipStream_t st);
 void launch_scan(const uint32_t* in, uint32_t* out, uint32_t* part, uint32_t n, hipStream_t st);  // route.hip

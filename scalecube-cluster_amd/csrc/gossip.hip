@@ -1279,20 +1279,23 @@ constexpr uint32_t SEND_GRID = 4096;  // 16 blocks per CU, grid-stride
 
 // the sends of this tick and the holder-state changes they need, up to the first receipts (the sharded tick
 // exchanges them before launch_gossip_apply)
-void launch_gossip_send(const Dev& d, uint32_t k, hipStream_t st, const TickEvents* prof) {
+void launch_gossip_send(const Dev& d, uint32_t k, hipStream_t st, const TickEvents* prof,
+                        const GossipChunks* chunks) {
   hipLaunchKernelGGL(k_gossip_groups, dim3(1), dim3(1024), 0, st, d);
   hipLaunchKernelGGL(k_round_plan, dim3(cdiv(d.N, 256)), dim3(256), 0, st, d, k);
   launch_scan(d.tin_cnt, d.tin_off, d.scan_part, d.N, st);
   hipLaunchKernelGGL(k_tin_scatter, dim3(cdiv(d.N, 256)), dim3(256), 0, st, d);
   {  // LDS rows sized by the slot table (the active span never exceeds QW words)
-    const uint32_t cw = std::min<uint32_t>(RCS, d.QW), cb = std::min<uint32_t>(RCW, d.QW);
+    // (chunks: the known-answer tests' sizes, engine.h GossipChunks)
+    const uint32_t cw = chunks && chunks->cw ? chunks->cw : std::min<uint32_t>(RCS, d.QW);
+    const uint32_t cb = chunks && chunks->cb ? chunks->cb : std::min<uint32_t>(RCW, d.QW);
     hipLaunchKernelGGL(k_round_apply_w, dim3(4096), dim3(256), 4 * 2 * 8 * cw, st, d.self, k, cw);
     hipLaunchKernelGGL(k_round_apply_b, dim3(2048), dim3(256), 2 * 8 * cb, st, d.self, k, cb, cw);
   }
   hipLaunchKernelGGL(k_gossip_contacts, dim3(2048), dim3(256), 0, st, d, k);
   hipLaunchKernelGGL(k_contact_cache, dim3(1024), dim3(256), 0, st, d.self, k);
   {
-    const uint32_t cx = std::min<uint32_t>(RXW, d.QW);
+    const uint32_t cx = chunks && chunks->cx ? chunks->cx : std::min<uint32_t>(RXW, d.QW);
     hipLaunchKernelGGL(k_rx_build, dim3(512), dim3(256), 8 * cx, st, d.self, cx);
   }
   if (prof && prof->all) hipEventRecord((hipEvent_t)prof->ev[4], st);

@@ -1,7 +1,8 @@
 // selftest.hip — swim_selftest_eval (include/swimhip_selftest.h): the device primitives the simulation kernels call,
 // evaluated on caller inputs in a gfx950 kernel, so the reference's known answers pin the device code itself; and
 // swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives and the SYNC diff with its
-// lister the same way, and the row-shard exchange codec (shard.hip) in the engine's own grids (engine only).
+// lister the same way, and the row-shard exchange codec (shard.hip) and the gossip data plane's per-tick kernels
+// (gossip.hip) in the engine's own grids (engine only).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1032,13 +1033,187 @@ int prim_inline_in(const uint32_t* P, size_t np, const uint32_t* in, size_t inb,
   return bf.rc;
 }
 
+// launch_gossip_send and (GS_APPLY) launch_gossip_apply for one tick on caller-built holder state (one GPU, no link delays)
+int prim_gossip(const uint32_t* P, size_t np, const uint32_t* in, size_t inb, uint32_t* out, size_t outb) {
+  if (np != 27) return SWIM_EINVAL;
+  const uint32_t N = P[0], F = P[1], SLOTS = P[2], BCAP = P[3], LOGW = P[4], lat = P[5], gossip_t = P[6], EXPB = P[7], k = P[8],
+                 rr_atomic = P[11], cev_cap = P[12], CRCAP = P[13], RPCAP = P[14], SLOWCAP = P[15], RCAP = P[16], HCAP = P[17],
+                 sort_cap = P[18], rank = P[19], SPR = P[20], fl = P[21], ep_loss = P[25], ep_part = P[26];
+  const GossipChunks chunks{P[22], P[23], P[24]};
+  const bool apply = fl & SWIM_PRIM_GS_APPLY;
+  if (N < 1 || N > 4096 || F < 1 || F > 8 || (SLOTS & 63u) || SLOTS < 64 || SLOTS > (1u << 18) || (uint64_t)N * SLOTS > (1u << 21) ||
+      !pow2(BCAP) || BCAP > 16384 || (uint64_t)N * BCAP > PRIM_MAX || !pow2(LOGW) || LOGW > 256 || lat > (1u << 16) || gossip_t < 1 ||
+      gossip_t > (1u << 16) || EXPB > (1u << 20) || k < 1 || k >= (1u << 30) || cev_cap > CEV || CRCAP < 1 || CRCAP > 4096 ||
+      (uint64_t)CRCAP * (SLOTS / 64) > PRIM_MAX || RPCAP < 1 || RPCAP > (1u << 20) || SLOWCAP < 1 || SLOWCAP > (1u << 20) || RCAP < 1 ||
+      RCAP > PRIM_MAX || !pow2(HCAP) || HCAP > (1u << 16) || !pow2(sort_cap) || sort_cap < 2 || sort_cap > SORT_MAX || SPR < 1 ||
+      rank >= 64 || fl > 7 || ep_loss > 100 || ep_part > 1 ||
+      // the staged kernels' dynamic LDS (64 KB per workgroup): 4 waves x 2 rows x cw, 2 rows x cb, 1 row x cx words
+      chunks.cw > 1024 || chunks.cb > 4096 || chunks.cx > 8192)
+    return SWIM_EINVAL;
+  const uint32_t QW = SLOTS / 64, NS = key_plane_sizes(N).NS;
+  const uint64_t NF = (uint64_t)N * F, NL = (uint64_t)N * LOGW;
+  auto pad8 = [](uint64_t b) { return (b + 7u) & ~7ull; };
+
+  // ---- the layouts: every array starts 8-byte aligned (its bytes rounded up to a multiple of 8) ----
+  const uint64_t b_in = 16ull * SLOTS + 2 * pad8(4ull * SLOTS) + 7 * pad8(4ull * N) + pad8(4 * NF) + 3 * pad8(4 * NL) +
+                        pad8(4 * NL * F) + 2 * pad8(4ull * N) + (apply ? pad8(4ull * N * NS) : 0);
+  const uint64_t b_out = 16ull * QW + 16ull * N * QW + 8ull * CRCAP * QW + 8ull * RPCAP + 8ull * SLOWCAP + 8ull * HCAP * HREC +
+                         16ull * RCAP + 8 + 16ull * N + 8ull * FB_N + pad8(2ull * N * SLOTS) + pad8(4ull * N * BCAP) +
+                         21 * pad8(4ull * N) + 4 * pad8(4ull * SLOTS) + pad8(4ull * QW) + 4 * pad8(4 * NF) + pad8(4 * NF * CEVW) +
+                         pad8(12ull * CRCAP) + pad8(4ull * RCAP) + 64 + 32;
+  if (inb != b_in || outb != b_out) return SWIM_EINVAL;
+  Cursor ci{(uint8_t*)in}, co{(uint8_t*)out};
+  auto in4 = [&](uint64_t n) { return (const uint32_t*)ci.take(pad8(4 * n)); };
+  const uint64_t* i_gid = (const uint64_t*)ci.take(8ull * SLOTS);
+  const uint64_t* i_key = (const uint64_t*)ci.take(8ull * SLOTS);
+  const uint32_t *i_subj = in4(SLOTS), *i_ctick = in4(SLOTS), *i_first = in4(N), *i_tround = in4(N), *i_tcnt = in4(N),
+                 *i_tspread = in4(N), *i_tperiod = in4(N), *i_spchg = in4(N), *i_lpos = in4(N), *i_T = in4(NF), *i_ltick = in4(NL),
+                 *i_lspread = in4(NL), *i_lcnt = in4(NL), *i_ltg = in4(NL * F), *i_group = in4(N), *i_leaving = in4(N),
+                 *i_rowk = apply ? in4((uint64_t)N * NS) : nullptr;
+  auto out8 = [&](uint64_t n) { return (uint64_t*)co.take(8 * n); };
+  auto out4 = [&](uint64_t n) { return (uint32_t*)co.take(pad8(4 * n)); };
+  uint64_t *o_gu = out8(QW), *o_dm = out8(QW), *o_hb = out8((uint64_t)N * QW), *o_wb = out8((uint64_t)N * QW),
+           *o_rx = out8((uint64_t)CRCAP * QW), *o_rp = out8(RPCAP), *o_slow = out8(SLOWCAP), *o_hist = out8((uint64_t)HCAP * HREC),
+           *o_raw = out8(RCAP), *o_rkey = out8(RCAP), *o_ctr = out8(1), *o_em = out8(2ull * N), *o_fb = out8(FB_N);
+  uint16_t* o_S = (uint16_t*)co.take(pad8(2ull * N * SLOTS));
+  uint32_t *o_rg = out4((uint64_t)N * BCAP), *o_dead = out4(N), *o_rhead = out4(N), *o_rtail = out4(N), *o_rwin = out4(N),
+           *o_rseen = out4(N), *o_held = out4(N), *o_rsend = out4(N), *o_rwnew = out4(N), *o_rt0 = out4(N), *o_tcs = out4(N),
+           *o_tcnt = out4(N), *o_tfill = out4(N), *o_toff = out4(N), *o_drx = out4(N), *o_ndrop = out4(N), *o_rwl = out4(N),
+           *o_tlist = out4(N), *o_ap = out4(N), *o_roff = out4(N), *o_rcnt = out4(N), *o_sg = out4(N), *o_exp = out4(SLOTS),
+           *o_used = out4(SLOTS), *o_fexp = out4(SLOTS), *o_free = out4(SLOTS), *o_agroup = out4(QW), *o_tin = out4(NF),
+           *o_tcontact = out4(NF), *o_cin = out4(NF), *o_crow = out4(NF), *o_cev = out4(NF * CEVW), *o_rxl = out4(3ull * CRCAP),
+           *o_rslot = out4(RCAP), *o_sc = out4(16), *o_err = out4(8);
+
+  // ---- host checks: everything the kernels index with ----
+  uint64_t used = 0;
+  for (uint32_t q = 0; q < QW; ++q) used += (uint64_t)__builtin_popcountll(o_gu[q]);
+  const int32_t free_top = (int32_t)o_sc[11];
+  if (free_top < 0 || (uint64_t)free_top + used > SLOTS || o_sc[7] != 0) return SWIM_EINVAL;  // sc[7]: rc_n starts a tick at 0
+  for (uint32_t g = 0; g < SLOTS; ++g)
+    if (i_subj[g] != USER_SUBJ && i_subj[g] >= N) return SWIM_EINVAL;
+  for (uint32_t m = 0; m < N; ++m) {
+    if (i_tcnt[m] > F) return SWIM_EINVAL;
+    for (uint32_t s = 0; s < i_tcnt[m]; ++s)
+      if (i_T[(uint64_t)m * F + s] >= N) return SWIM_EINVAL;
+    for (uint32_t e = 0; e < LOGW; ++e) {
+      const uint64_t li = (uint64_t)m * LOGW + e;
+      if (i_lcnt[li] > F) return SWIM_EINVAL;
+      for (uint32_t s = 0; s < i_lcnt[li]; ++s)
+        if (i_ltg[li * F + s] >= N) return SWIM_EINVAL;
+    }
+    const uint32_t h = o_rhead[m], len = o_rtail[m] - h;  // positions are absolute and may wrap: differences only
+    if (len > BCAP || o_rwin[m] - h > len || o_rseen[m] - h > len) return SWIM_EINVAL;
+    for (uint32_t j = 0; j < len; ++j)
+      if ((o_rg[(uint64_t)m * BCAP + ((h + j) & (BCAP - 1))] & RG_SLOT) >= SLOTS) return SWIM_EINVAL;
+  }
+
+  // ---- the Dev: only the fields the two launchers' kernels read ----
+  PrimBufs bf;
+  Dev d;
+  memset(&d, 0, sizeof d);
+  d.N = N, d.NS = NS, d.F = F, d.SLOTS = SLOTS, d.QW = QW, d.BCAP = BCAP, d.LOGW = LOGW, d.lat = lat, d.gossip_t = gossip_t;
+  d.gt_mul = gt_mul_of(gossip_t), d.EXPB = EXPB, d.seed_lo = P[9], d.seed_hi = P[10], d.rr_atomic = rr_atomic, d.cev_cap = cev_cap;
+  d.CRCAP = CRCAP, d.RPCAP = RPCAP, d.SLOWCAP = SLOWCAP, d.RCAP = RCAP, d.HCAP = HCAP, d.sort_cap = sort_cap, d.rank = rank, d.SPR = SPR;
+  d.W = d.XW = 1, d.lo = 0, d.hi = N, d.NL = N;
+  for (uint32_t e = 0; e < MAX_EPOCHS; ++e) d.ep_from[e] = e ? NEVER : 0u;  // one settings epoch
+  d.ep_loss[0] = ep_loss, d.ep_part[0] = ep_part;
+  d.slot_gid = bf.get<uint64_t>(SLOTS, i_gid, SLOTS);
+  d.slot_key = bf.get<uint64_t>(SLOTS, i_key, SLOTS);
+  d.slot_subj = bf.get<uint32_t>(SLOTS, i_subj, SLOTS);
+  d.slot_ctick = bf.get<uint32_t>(SLOTS, i_ctick, SLOTS);
+  d.firstGossip = bf.get<uint32_t>(N, i_first, N);
+  d.tround = bf.get<uint32_t>(N, i_tround, N);
+  d.tcnt = bf.get<uint32_t>(N, i_tcnt, N);
+  d.tspread = bf.get<uint32_t>(N, i_tspread, N);
+  d.tperiod = bf.get<uint32_t>(N, i_tperiod, N);
+  d.spchg = bf.get<uint32_t>(N, i_spchg, N);
+  d.log_pos = bf.get<uint32_t>(N, i_lpos, N);
+  d.T = bf.get<uint32_t>(NF, i_T, NF);
+  d.log_tick = bf.get<uint32_t>(NL, i_ltick, NL);
+  d.log_spread = bf.get<uint32_t>(NL, i_lspread, NL);
+  d.log_cnt = bf.get<uint32_t>(NL, i_lcnt, NL);
+  d.log_tg = bf.get<uint32_t>(NL * F, i_ltg, NL * F);
+  d.ep_group = bf.get<uint32_t>((uint64_t)MAX_EPOCHS * N, i_group, N);
+  d.leaving = bf.get<uint32_t>(N, i_leaving, N);
+  d.rowk = apply ? bf.get<uint32_t>((uint64_t)N * NS, i_rowk, (uint64_t)N * NS) : nullptr;
+  // in/out: loaded from the caller's words, copied back after the launches
+  struct Back {
+    void* host;
+    const void* dev;
+    uint64_t bytes;
+  };
+  std::vector<Back> backs;
+  auto io8 = [&](uint64_t* h, uint64_t n) {
+    unsigned long long* p = bf.get<unsigned long long>(n, h, n);
+    backs.push_back({h, p, 8 * n});
+    return p;
+  };
+  auto io4 = [&](uint32_t* h, uint64_t n) {
+    uint32_t* p = bf.get<uint32_t>(n, h, n);
+    backs.push_back({h, p, 4 * n});
+    return p;
+  };
+  d.GU = io8(o_gu, QW), d.DM = io8(o_dm, QW), d.HB = io8(o_hb, (uint64_t)N * QW), d.WB = io8(o_wb, (uint64_t)N * QW);
+  d.RX = io8(o_rx, (uint64_t)CRCAP * QW);
+  d.rp = (uint64_t*)io8(o_rp, RPCAP), d.slow = (uint64_t*)io8(o_slow, SLOWCAP), d.hist = (uint64_t*)io8(o_hist, (uint64_t)HCAP * HREC);
+  d.rc_raw = (uint64_t*)io8(o_raw, RCAP), d.rc_key = (uint64_t*)io8(o_rkey, RCAP);
+  d.ctr = bf.get<unsigned long long>(C_NCTR);
+  unsigned long long* em = bf.get<unsigned long long>(2ull * N, o_em, 2ull * N);
+  unsigned long long* fb = bf.get<unsigned long long>(FB_N, o_fb, FB_N);
+  d.em = fl & SWIM_PRIM_GS_EM ? em : nullptr;
+  d.fb = fl & SWIM_PRIM_GS_FB ? fb : nullptr;
+  backs.push_back({o_em, em, 16ull * N});
+  backs.push_back({o_fb, fb, 8ull * FB_N});
+  d.S = bf.get<uint16_t>((uint64_t)N * SLOTS, o_S, (uint64_t)N * SLOTS);
+  backs.push_back({o_S, d.S, 2ull * N * SLOTS});
+  d.rg = io4(o_rg, (uint64_t)N * BCAP);
+  d.dead_tick = io4(o_dead, N), d.rhead = io4(o_rhead, N), d.rtail = io4(o_rtail, N), d.rwin = io4(o_rwin, N), d.rseen = io4(o_rseen, N);
+  d.held = io4(o_held, N), d.rsend = io4(o_rsend, N), d.rwnew = io4(o_rwnew, N), d.rt0 = io4(o_rt0, N);
+  d.tin_cnt = bf.get<uint32_t>(N);  // the senders' lists are empty between ticks
+  d.tin_fill = bf.get<uint32_t>(N);
+  backs.push_back({o_tcnt, d.tin_cnt, 4ull * N});
+  backs.push_back({o_tfill, d.tin_fill, 4ull * N});
+  d.tin_off = io4(o_toff, N), d.dead_rx = io4(o_drx, N), d.rc_ndrop = io4(o_ndrop, N), d.rwl = io4(o_rwl, N), d.tlist = io4(o_tlist, N);
+  d.ap_list = io4(o_ap, N), d.rc_off = io4(o_roff, N);
+  d.rc_cnt = bf.get<uint32_t>(N);
+  d.rc_fill = bf.get<uint32_t>(N);
+  backs.push_back({o_rcnt, d.rc_cnt, 4ull * N});
+  d.sg_list = io4(o_sg, N);
+  d.slot_exp = io4(o_exp, SLOTS), d.slot_used = io4(o_used, SLOTS), d.fexp = io4(o_fexp, SLOTS), d.free_list = io4(o_free, SLOTS);
+  d.agroup = io4(o_agroup, QW), d.tin = io4(o_tin, NF), d.tcontact = io4(o_tcontact, NF), d.cin = io4(o_cin, NF), d.crow = io4(o_crow, NF);
+  d.cev = io4(o_cev, NF * CEVW), d.rxl = io4(o_rxl, 3ull * CRCAP), d.rc_slot = io4(o_rslot, RCAP);
+  uint32_t* sc = io4(o_sc, 16);  // nagroup[2], nrwl, ntl, nrx, rp_n, slow_n, rc_n, nap, nsg, nfexp, free_top, hist_n, ncfl, xd_n, 0
+  d.nagroup = sc, d.nrwl = sc + 2, d.ntl = sc + 3, d.nrx = sc + 4, d.rp_n = sc + 5, d.slow_n = sc + 6, d.rc_n = sc + 7, d.nap = sc + 8;
+  d.nsg = sc + 9, d.nfexp = sc + 10, d.free_top = (int32_t*)(sc + 11), d.hist_n = sc + 12, d.ncfl = sc + 13, d.xd_n = sc + 14;
+  d.err = bf.get<uint32_t>(8);
+  d.cfl = bf.get<uint32_t>(NF);
+  d.scan_part = bf.get<uint32_t>(1024);
+  d.rc_key2 = bf.get<uint64_t>(RCAP);
+  d.rc_slot2 = bf.get<uint32_t>(RCAP);
+  Dev* self = bf.get<Dev>(1);
+  d.self = self;
+  if (bf.rc == SWIM_OK && hipMemcpy(self, &d, sizeof d, hipMemcpyHostToDevice) != hipSuccess) bf.rc = SWIM_EDEVICE;
+  if (bf.rc != SWIM_OK) return bf.rc;
+
+  launch_gossip_send(d, k, 0, nullptr, &chunks);
+  if (!bf.ran() || !bf.back(o_tcs, d.tin_cnt, 4ull * N)) return bf.rc;  // before k_gossip_apply clears it
+  if (apply) {
+    launch_gossip_apply(d, k, 0);
+    if (!bf.ran()) return bf.rc;
+  }
+  for (const Back& b : backs)
+    if (!bf.back(b.host, b.dev, b.bytes)) return bf.rc;
+  if (bf.back(o_ctr, d.ctr + C_G, 8)) bf.back(o_err, d.err, 32);
+  return bf.rc;
+}
+
 }  // namespace
 }  // namespace swim
 
 extern "C" int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t n_params, const void* in, size_t in_bytes,
                                     void* out, size_t out_bytes, uint32_t device) {
   using namespace swim;
-  if (op > SWIM_PRIM_XUNPACK || !params || n_params > 32 || !out || (in_bytes && !in) || ((uintptr_t)in & 7u) ||
+  if (op > SWIM_PRIM_GOSSIP || !params || n_params > 32 || !out || (in_bytes && !in) || ((uintptr_t)in & 7u) ||
       ((uintptr_t)out & 7u))
     return SWIM_EINVAL;
   int ndev = 0;
@@ -1059,6 +1234,7 @@ extern "C" int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t 
     case SWIM_PRIM_XPACK: return prim_xpack(params, n_params, i32, in_bytes, o32, out_bytes);
     case SWIM_PRIM_PACK_B: return prim_pack_b(params, n_params, i32, in_bytes, o32, out_bytes);
     case SWIM_PRIM_INLINE_IN: return prim_inline_in(params, n_params, i32, in_bytes, o32, out_bytes);
-    default: return prim_xunpack(params, n_params, i32, in_bytes, o32, out_bytes);
+    case SWIM_PRIM_XUNPACK: return prim_xunpack(params, n_params, i32, in_bytes, o32, out_bytes);
+    default: return prim_gossip(params, n_params, i32, in_bytes, o32, out_bytes);
   }
 }

@@ -252,7 +252,9 @@ DEBUG_SIGNATURES = {
 }
 # swim_debug_prim_eval: ops, and the sub-ops of PRIM_WAVE and PRIM_ARITH (include/swimhip_debug.h has the layouts)
 (PRIM_SCAN, PRIM_SEG_SORT, PRIM_ROUTING, PRIM_WAVE, PRIM_DIRTY, PRIM_ARITH, PRIM_FEISTEL, PRIM_RING_MOVE,
- PRIM_SYNC_DIFF, PRIM_XPACK, PRIM_PACK_B, PRIM_INLINE_IN, PRIM_XUNPACK) = range(13)
+ PRIM_SYNC_DIFF, PRIM_XPACK, PRIM_PACK_B, PRIM_INLINE_IN, PRIM_XUNPACK, PRIM_GOSSIP) = range(14)
+# PRIM_GOSSIP's flags (SWIM_PRIM_GS_*)
+(GS_APPLY, GS_EM, GS_FB) = (1, 2, 4)
 # PRIM_XPACK's flags (SWIM_PRIM_XP_*)
 (XP_ACKRES, XP_INLINE, XP_SPEC, XP_HALTED, XP_TLOG, XP_INLINE_OUT) = (1, 2, 4, 8, 16, 32)
 # PRIM_XUNPACK's flags (SWIM_PRIM_XU_*)

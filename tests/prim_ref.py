@@ -1483,3 +1483,944 @@ def inline_in_ref(W, XI, cap, irecv, scnt, halted):
             recv[p][:n] = irecv[p][8:8 + n]
             rcnt[p], host[p], host[W + p] = w, scnt[p], w
     return recv, rcnt, host
+
+
+# ---------------------------------------------------------------------------------------------- Philox4x32-10
+def philox(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 over numpy arrays (swim_common.h philox); known answers in tests/test_gpu_c5_scale.py."""
+    m = np.uint64(M32)
+    c = [np.asarray(x, dtype=np.uint64) & m for x in (c0, c1, c2, c3)]
+    k0, k1 = np.uint64(k0), np.uint64(k1)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & m, p1 & m, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & m, p0 & m]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & m
+        k1 = (k1 + np.uint64(0xBB67AE85)) & m
+    return c
+
+
+def mix64(z):
+    z = (z + 0x9E3779B97F4A7C15) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+# ---------------------------------------------------------------------------------------------- gossip data plane
+# SWIM_PRIM_GOSSIP (include/swimhip_debug.h): launch_gossip_send and launch_gossip_apply for one tick k on a holder state
+# built here. A state is a dict of the op's params and numpy arrays under the names of engine.h; gs_ref states what the
+# tick does to it member by member with Python sets of slot ids, never with the kernels' word arithmetic.
+GS_SENT = 0xA5A5A5A5
+GS_SENT64 = GS_SENT | GS_SENT << 32
+GS_APPLY, GS_EM, GS_FB = 1, 2, 4
+CEV, CEVW, HREC, HKEEP, FB_N, SLIFE, APPLY_LANE = 6, 22, 11, 16, 16, 4096, 8
+S16_SWEPT, S16_REBORN = 1 << 14, 1 << 15
+E_RECEIPTS, E_CONTACTS, E_RING, E_SLIFE = 1024, 2048, 1 << 22, 1 << 25
+SALT_LOSS_GOSSIP = 0x474F5353
+FB_CEV_SLOW, FB_REPLAY, FB_RX_ALL = 4, 5, 8
+GS_PARAMS = ("N", "F", "SLOTS", "BCAP", "LOGW", "lat", "gossip_t", "EXPB", "k", "seed_lo", "seed_hi", "rr_atomic", "cev_cap",
+             "CRCAP", "RPCAP", "SLOWCAP", "RCAP", "HCAP", "sort_cap", "rank", "SPR", "flags", "cw", "cb", "cx", "ep_loss", "ep_part")
+GS_SC = ("nag", "span", "nrwl", "ntl", "nrx", "rp_n", "slow_n", "rc_n", "nap", "nsg", "nfexp", "free_top", "hist_n", "ncfl",
+         "xd_n", "pad")
+# the paths of k_round_apply_w / _b one round state runs through (5-word rows and up: cw = 2 sends them to the workgroup
+# kernel, cb then gives its chunks); QW is the state's
+GS_PATHS = {"atomic": dict(rr_atomic=1 << 31), "wave": dict(rr_atomic=0), "block1": dict(rr_atomic=0, cw=2),
+            "block2": dict(rr_atomic=0, cw=2, cb=lambda QW: (QW + 1) // 2 + (QW % 2 == 0)),
+            "block3": dict(rr_atomic=0, cw=2, cb=lambda QW: (QW + 2) // 3)}
+
+
+def gs_layout(c):
+    """(in fields, out fields) as (name, dtype, elements); every array starts 8-byte aligned."""
+    N, F, SLOTS, BCAP, LOGW = c["N"], c["F"], c["SLOTS"], c["BCAP"], c["LOGW"]
+    QW, NF, NL, NS = SLOTS // 64, N * F, N * LOGW, (N + 7) & ~7
+    u4, u8 = np.uint32, np.uint64
+    inp = [("slot_gid", u8, SLOTS), ("slot_key", u8, SLOTS), ("slot_subj", u4, SLOTS), ("slot_ctick", u4, SLOTS)]
+    inp += [(n, u4, N) for n in ("firstGossip", "tround", "tcnt", "tspread", "tperiod", "spchg", "log_pos")]
+    inp += [("T", u4, NF), ("log_tick", u4, NL), ("log_spread", u4, NL), ("log_cnt", u4, NL), ("log_tg", u4, NL * F),
+            ("ep_group", u4, N), ("leaving", u4, N)]
+    if c["flags"] & GS_APPLY:
+        inp.append(("rowk", u4, N * NS))
+    out = [("GU", u8, QW), ("DM", u8, QW), ("HB", u8, N * QW), ("WB", u8, N * QW), ("RX", u8, c["CRCAP"] * QW), ("rp", u8, c["RPCAP"]),
+           ("slow", u8, c["SLOWCAP"]), ("hist", u8, c["HCAP"] * HREC), ("rc_raw", u8, c["RCAP"]), ("rc_key", u8, c["RCAP"]),
+           ("ctr_g", u8, 1), ("em", u8, 2 * N), ("fb", u8, FB_N), ("S", np.uint16, N * SLOTS), ("rg", u4, N * BCAP)]
+    out += [(n, u4, N) for n in ("dead_tick", "rhead", "rtail", "rwin", "rseen", "held", "rsend", "rwnew", "rt0", "tin_cnt_send",
+                                 "tin_cnt", "tin_fill", "tin_off", "dead_rx", "rc_ndrop", "rwl", "tlist", "ap_list", "rc_off",
+                                 "rc_cnt", "sg_list")]
+    out += [(n, u4, SLOTS) for n in ("slot_exp", "slot_used", "fexp", "free_list")]
+    out += [("agroup", u4, QW), ("tin", u4, NF), ("tcontact", u4, NF), ("cin", u4, NF), ("crow", u4, NF), ("cev", u4, NF * CEVW),
+            ("rxl", u4, 3 * c["CRCAP"]), ("rc_slot", u4, c["RCAP"]), ("sc", u4, 16), ("err", u4, 8)]
+    return inp, out
+
+
+def _gs_blob(c, fields):
+    parts = []
+    for name, dt, n in fields:
+        if name in c:
+            a = np.ascontiguousarray(c[name], dtype=dt).reshape(-1)
+        else:  # an output the caller has nothing to say about: the sentinel shows what was not written
+            a = np.full(n, GS_SENT64 if dt == np.uint64 else GS_SENT & (0xFFFF if dt == np.uint16 else M32), dt)
+        assert a.size == n, (name, a.size, n)
+        b = a.view(np.uint8)
+        parts.append(b)
+        if b.size % 8:
+            parts.append(np.zeros(8 - b.size % 8, np.uint8))
+    return np.concatenate(parts).view(np.uint64)
+
+
+def gs_pack(c):
+    """(params, in, out) of SWIM_PRIM_GOSSIP for state c."""
+    inp, out = gs_layout(c)
+    sc = np.full(16, GS_SENT, np.uint32)
+    sc[[GS_SC.index("rc_n"), GS_SC.index("hist_n")]] = 0
+    sc[GS_SC.index("free_top")] = c["free_top"]
+    return [c[p] for p in GS_PARAMS], _gs_blob(c, inp), _gs_blob(dict(c, sc=sc, em=np.zeros(2 * c["N"], np.uint64),
+                                                                     fb=np.zeros(FB_N, np.uint64)), out)
+
+
+def gs_unpack(c, out):
+    N, F, SLOTS, BCAP, QW = c["N"], c["F"], c["SLOTS"], c["BCAP"], c["SLOTS"] // 64
+    b, o, r = out.view(np.uint8), 0, {}
+    for name, dt, n in gs_layout(c)[1]:
+        nb = n * np.dtype(dt).itemsize
+        r[name] = b[o:o + nb].view(dt).copy()
+        o += (nb + 7) & ~7
+    assert o == b.size
+    for name, shape in (("HB", (N, QW)), ("WB", (N, QW)), ("S", (N, SLOTS)), ("rg", (N, BCAP)), ("RX", (c["CRCAP"], QW)),
+                        ("cev", (N * F, CEVW)), ("hist", (c["HCAP"], HREC)), ("rxl", (c["CRCAP"], 3))):
+        r[name] = r[name].reshape(shape)
+    r.update({n: int(r["sc"][i]) for i, n in enumerate(GS_SC)})
+    r["free_top"] -= (r["free_top"] >> 31) << 32
+    return r
+
+
+def gs_bits(words):
+    """The set of bit indices set in a row of u64 words."""
+    out = set()
+    for q, w in enumerate(np.asarray(words).tolist()):
+        while w:
+            b = w & -w
+            out.add(q * 64 + b.bit_length() - 1)
+            w ^= b
+    return out
+
+
+def gs_words(slots, QW):
+    row = [0] * QW
+    for g in slots:
+        row[g >> 6] |= 1 << (g & 63)
+    return np.array(row, np.uint64)
+
+
+def gs_new(N, SLOTS, k=9000, F=8, BCAP=64, LOGW=4, **kw):
+    """An idle plane: no slot in use, every ring empty, no round this tick, empty round logs."""
+    c = dict(N=N, F=F, SLOTS=SLOTS, BCAP=BCAP, LOGW=LOGW, lat=1, gossip_t=2, EXPB=40, k=k, seed_lo=0x1234ABCD, seed_hi=0x0BADF00D,
+             rr_atomic=64, cev_cap=CEV, CRCAP=8, RPCAP=64, SLOWCAP=64, RCAP=64, HCAP=64, sort_cap=64, rank=0, SPR=SLOTS, flags=0,
+             cw=0, cb=0, cx=0, ep_loss=0, ep_part=0, free_top=0)
+    c.update(kw)
+    QW, NS = SLOTS // 64, (N + 7) & ~7
+    z = lambda *s: np.zeros(s, np.uint32)
+    c.update(slot_gid=np.zeros(SLOTS, np.uint64), slot_key=np.zeros(SLOTS, np.uint64), slot_subj=np.full(SLOTS, USER_SUBJ, np.uint32),
+             slot_ctick=z(SLOTS), firstGossip=z(N), tround=z(N), tcnt=z(N), tspread=z(N), tperiod=z(N), spchg=z(N), log_pos=z(N),
+             T=np.full((N, F), NEVER, np.uint32), log_tick=np.full((N, LOGW), NEVER, np.uint32), log_spread=z(N, LOGW),
+             log_cnt=z(N, LOGW), log_tg=np.full((N, LOGW, F), NEVER, np.uint32), ep_group=z(N), leaving=z(N), rowk=z(N, NS),
+             GU=np.zeros(QW, np.uint64), DM=np.zeros(QW, np.uint64), HB=np.zeros((N, QW), np.uint64), WB=np.zeros((N, QW), np.uint64),
+             hist=np.zeros((c["HCAP"], HREC), np.uint64), S=np.zeros((N, SLOTS), np.uint16), rg=np.full((N, BCAP), GS_SENT, np.uint32),
+             dead_tick=np.full(N, NEVER, np.uint32), rhead=z(N), rtail=z(N), rwin=z(N), rseen=z(N), held=z(N), dead_rx=z(N),
+             rc_ndrop=z(N), slot_exp=z(SLOTS), slot_used=z(SLOTS), free_list=np.full(SLOTS, GS_SENT, np.uint32))
+    return c
+
+
+def gs_variant(c, **kw):
+    """The same state with other params (arrays shared: no reference or launch writes them)."""
+    v = dict(c)
+    for n, x in kw.items():
+        v[n] = x(c["SLOTS"] // 64) if callable(x) else x
+    return v
+
+
+def gs_use(c, g, gid, subj=USER_SUBJ, key=0, ctick=None, exp=None):
+    """Slot g carries gossip gid (created at ctick, recycled at exp); a DEAD membership record sets its DM bit."""
+    c["slot_gid"][g], c["slot_subj"][g], c["slot_key"][g], c["slot_used"][g] = gid, subj, key, 1
+    c["slot_ctick"][g] = c["k"] - 20 if ctick is None else ctick
+    c["slot_exp"][g] = c["k"] + 30 if exp is None else exp
+    c["GU"][g >> 6] |= np.uint64(1 << (g & 63))
+    if subj != USER_SUBJ and (key >> 32) & 3 == ST_DEAD:
+        c["DM"][g >> 6] |= np.uint64(1 << (g & 63))
+
+
+def gs_hold(c, m, g, period, ctick=None):
+    """Member m received slot g's gossip in its gossip period `period` (at tick ctick): ring entry, held bit, S entry."""
+    p = int(c["rtail"][m])
+    c["rg"][m][p & (c["BCAP"] - 1)] = rg_entry(g, period)
+    c["rtail"][m] = (p + 1) & M32
+    c["HB"][m][g >> 6] |= np.uint64(1 << (g & 63))
+    c["S"][m][g] = S16_EVER | ((c["k"] - 10 if ctick is None else ctick) & S16_TICK)
+    c["held"][m] += 1
+
+
+def gs_seen(c, m, win, seen):
+    """m's previous round left its window at ring offsets [win, seen) from rhead (entries past `seen` arrived since)."""
+    h = int(c["rhead"][m])
+    c["rwin"][m], c["rseen"][m] = (h + win) & M32, (h + seen) & M32
+    c["WB"][m] = gs_words([s for _, s, _ in gs_ring(c, m)[win:seen]], c["SLOTS"] // 64)
+
+
+def gs_round(c, m, P, spread, targets=()):
+    c["tround"][m], c["tperiod"][m], c["tspread"][m], c["tcnt"][m] = 1, P, spread, len(targets)
+    c["T"][m][:len(targets)] = targets
+    c["firstGossip"][m] = c["k"] - P * c["gossip_t"]  # rounds_before(m, k) = P
+
+
+def gs_period(tag, P):
+    """The one period within 512 of P whose low 10 bits are `tag`."""
+    return P + ((tag - P + 512) % 1024) - 512
+
+
+def gs_ring(c, m, P=None):
+    """m's live ring entries in order: (absolute position, slot, period as seen from period P)."""
+    P = int(c["tperiod"][m]) if P is None else P
+    h, n = int(c["rhead"][m]), (int(c["rtail"][m]) - int(c["rhead"][m])) & M32
+    es = [int(c["rg"][m][((h + j) & M32) & (c["BCAP"] - 1)]) for j in range(n)]
+    return [((h + j) & M32, e & RG_SLOT, gs_period(e >> 22, P)) for j, e in enumerate(es)]
+
+
+def gs_round_ref(c, m):
+    """Member m's round by classifying each ring entry: None if m has no round or the round changes nothing, else
+    dict(send, wnew, swept slots, window slots)."""
+    if not c["tround"][m]:
+        return None
+    P, sp, ring = int(c["tperiod"][m]), int(c["tspread"][m]), gs_ring(c, m)
+    swept = [s for _, s, p in ring if p < P - 2 * (sp + 1)]
+    before = [s for _, s, p in ring if p < P - sp]
+    h, tl = int(c["rhead"][m]), int(c["rtail"][m])
+    send, wnew = (h + len(swept)) & M32, (h + len(before)) & M32
+    if send == h and wnew == int(c["rwin"][m]) and int(c["rseen"][m]) == tl:
+        return None
+    return dict(send=send, wnew=wnew, swept=swept, window=[s for _, s, _ in ring[len(before):]])
+
+
+def gs_round_ref_ranges(c, m):
+    """The same by searching the sorted periods (the second formulation test_prim_ref.py compares with)."""
+    if not c["tround"][m]:
+        return None
+    P, sp, ring = int(c["tperiod"][m]), int(c["tspread"][m]), gs_ring(c, m)
+    per = np.array([p for _, _, p in ring], np.int64)
+    a, b = int(np.searchsorted(per, P - 2 * (sp + 1), "left")), int(np.searchsorted(per, P - sp, "left"))
+    h = int(c["rhead"][m])
+    if a == 0 and (h + b) & M32 == int(c["rwin"][m]) and c["rseen"][m] == c["rtail"][m]:
+        return None
+    slots = [s for _, s, _ in ring]
+    return dict(send=(h + a) & M32, wnew=(h + b) & M32, swept=slots[:a], window=slots[b:])
+
+
+def gs_pct(c, m, t):
+    """NetworkEmulator's loss percent of a send m -> t at tick k."""
+    if c["k"] >= c["dead_tick"][t] or (c["ep_part"] and c["ep_group"][m] != c["ep_group"][t]):
+        return 100
+    return c["ep_loss"]
+
+
+def gs_lost(c, m, s, slots, pct):
+    """Which of m's sends of `slots` through target slot s are lost (LOSS_GOSSIP draw, SEMANTICS.md §2)."""
+    slots = list(slots)
+    if pct == 0 or not slots:
+        return set()
+    if pct >= 100:
+        return set(slots)
+    gid = c["slot_gid"][slots]
+    r = philox(np.full(len(slots), m), c["k"] ^ ((s >> 2) << 31), gid >> np.uint64(32), gid & np.uint64(M32),
+               c["seed_lo"] ^ SALT_LOSS_GOSSIP, c["seed_hi"])[s & 3]
+    return {g for g, x in zip(slots, ((r * np.uint64(100)) >> np.uint64(32)).tolist()) if x < pct}
+
+
+def gs_s_get(c, e, g, ref):
+    """The creation tick of S entry e of slot g read at tick ref, or None when it reads as never held."""
+    if not e & S16_EVER:
+        return None
+    t = ref - ((ref - (e & S16_TICK)) & S16_TICK)
+    return None if t < c["slot_ctick"][g] else t
+
+
+def gs_overrides(s1, i1, s0, i0):
+    """MembershipRecord.isOverrides (ABSENT 0, ALIVE 1, SUSPECT 2, DEAD 3)."""
+    if s0 == 0:
+        return s1 == 1
+    if s0 == 3:
+        return False
+    if s1 == 3:
+        return True
+    return s1 == 2 and s0 != 2 if i1 == i0 else i1 > i0
+
+
+def gs_hist_tag(gid, member):
+    return mix64(gid ^ ((member * 0x9E3779B97F4A7C15) & M64)) | 1
+
+
+def gs_hist_decode(hist):
+    """{(gid, member): (n, creation ticks kept)} of an incarnation-history table."""
+    out = {}
+    for e in np.asarray(hist).reshape(-1, HREC):
+        if int(e[0]):
+            gid, member, n = int(e[1]), int(e[2]) & M32, int(e[2]) >> 32
+            assert int(e[0]) == gs_hist_tag(gid, member) and (gid, member) not in out
+            out[gid, member] = (n, tuple(e[3:].view(np.uint32)[:min(n, HKEEP)].tolist()))
+    return out
+
+
+def gs_events(c, m, t):
+    """The contact events of the pair (m, T[m][s] = t) up to tick k - lat in both round logs, in the order (tick, side,
+    target slot): (tick, side, slot, the round's spread, loss percent, sender's rounds before it); side 0 is t -> m. And the
+    oldest tick of each wrapped log (0: never wrapped)."""
+    ev, oldest = [], []
+    for side, (frm, to) in enumerate(((t, m), (m, t))):
+        for e in range(c["LOGW"]):
+            t2 = int(c["log_tick"][frm][e])
+            if t2 == NEVER or t2 + c["lat"] > c["k"]:
+                continue
+            for s2 in range(int(c["log_cnt"][frm][e])):
+                if c["log_tg"][frm][e][s2] == to:
+                    pct = 100 if t2 >= c["dead_tick"][to] or (c["ep_part"] and c["ep_group"][frm] != c["ep_group"][to]) else c["ep_loss"]
+                    ev.append((t2, side, s2, int(c["log_spread"][frm][e]), pct,
+                               rounds_before(int(c["firstGossip"][frm]), t2, c["gossip_t"])))
+        ticks = [int(x) for x in c["log_tick"][frm] if x != NEVER]
+        oldest.append(min(ticks) if c["log_pos"][frm] > c["LOGW"] and ticks else 0)
+    return sorted(ev), oldest
+
+
+def gs_contacts_ref(c, r, window, rows=None):
+    """The contact stage for this tick's pairs. window[m]: m's window entries after its round as (slot, period) in ring
+    order. rows: the pairs that got an RX row when more than CRCAP wanted one (which ones is an atomic's order)."""
+    k, lat, gt, F = c["k"], c["lat"], c["gossip_t"], c["F"]
+    r.update(tcontact={}, cin={}, crow={}, cev={}, rx={}, fb=np.zeros(FB_N, np.int64))
+    split = []
+    for t, mss in r["tin"].items():
+        for ms in mss:
+            m = ms // F
+            cut = k - (int(c["tspread"][m]) + 1) * gt - lat
+            hit = any(t2 != NEVER and cut < t2 < k and m in c["log_tg"][t][e][:c["log_cnt"][t][e]].tolist()
+                      for e, t2 in enumerate(c["log_tick"][t].tolist()))
+            r["tcontact"][ms], r["cin"][ms] = int(hit), NEVER
+            if not hit:
+                continue
+            ev, oldest = gs_events(c, m, t)
+            over = len(ev) > min(CEV, c["cev_cap"])
+            ins = [e[0] for e in ev if e[1] == 0]
+            rec = [CEV + 1 if over else len(ev), oldest[0], oldest[1], NEVER if over or not ins else ins[-1]]
+            if not over:
+                for t2, side, s2, sp, pct, rb in ev:
+                    rec += [t2, s2 | side << 8 | pct << 9 | sp << 16, rb]
+            r["cev"][ms], r["crow"][ms] = rec, NEVER  # RX_ALL
+            if over:
+                r["cin"][ms] = 0xFFFFFFFE  # CIN_SLOW
+                continue
+            last_in = ins[-1]  # a flagged pair has one after the horizon
+            b1 = rounds_before(int(c["firstGossip"][m]), last_in + lat + 1, gt)
+            early = [g for g, p in window[m] if p <= b1]
+            if early:
+                r["cin"][ms] = last_in
+                if len(early) < len(window[m]):
+                    split.append((ms, early))
+    r["nrx"] = len(split)
+    granted = [ms for ms, _ in split][:c["CRCAP"]] if rows is None else sorted(rows)
+    assert len(granted) == min(len(split), c["CRCAP"]) and set(granted) <= {ms for ms, _ in split}
+    for ms, early in split:
+        if ms in granted:
+            r["rx"][ms] = (int(r["rwin"][ms // F]), (int(r["rwin"][ms // F]) + len(early)) & M32, set(early))
+        else:
+            r["fb"][FB_RX_ALL] += 1
+    r["ncfl"] = sum(r["tcontact"].values())
+
+
+def gs_ref(c, rows=None, dropped=()):
+    """What one tick leaves. Sends of pairs with a logged contact are diverted to the replay lists; here every diverted
+    gossip is one its target never held, so the replay's answer is `not in infectedFrom`: it is sent. rows, dropped: the
+    outcomes of the two capacity races (gs_contacts_ref; the list entries that found no place), taken from the run."""
+    N, F, QW, k, lat = c["N"], c["F"], c["SLOTS"] // 64, c["k"], c["lat"]
+    r = dict(err=0)
+    active = [q for q in range(QW) if c["GU"][q]]
+    r["agroup"], r["nag"], r["span"] = active, len(active), active[-1] + 1 if active else 0
+    # ---- rounds
+    HB, WB = [gs_bits(c["HB"][m]) for m in range(N)], [gs_bits(c["WB"][m]) for m in range(N)]
+    S = c["S"].copy()
+    for n in ("rhead", "rwin", "rseen", "held", "dead_tick", "dead_rx", "slot_exp", "slot_used", "rc_ndrop"):
+        r[n] = c[n].astype(np.int64)
+    r["rwl"], r["rsend"], r["rwnew"] = set(), {}, {}
+    for m in range(N):
+        rr = gs_round_ref(c, m)
+        if rr is None:
+            continue
+        r["rwl"].add(m)
+        r["rsend"][m], r["rwnew"][m] = rr["send"], rr["wnew"]
+        HB[m] -= set(rr["swept"])
+        WB[m] = set(rr["window"])
+        for g in rr["swept"]:
+            S[m][g] |= S16_SWEPT
+            if c["slot_gid"][g] >> np.uint64(32) == m and c["slot_subj"][g] == m and (int(c["slot_key"][g]) >> 32) & 3 == ST_DEAD:
+                r["dead_tick"][m] = k + 1  # its own leave notification: the leave completes
+        r["rhead"][m], r["rwin"][m], r["rseen"][m] = rr["send"], rr["wnew"], c["rtail"][m]
+        r["held"][m] -= len(rr["swept"])
+    # ---- scatter
+    pairs = [(int(c["T"][m][s]), m * F + s) for m in range(N) if c["tround"][m] for s in range(int(c["tcnt"][m]))]
+    r["tin"] = {t: sorted(ms for t2, ms in pairs if t2 == t) for t in set(t for t, _ in pairs)}
+    r["tin_cnt"] = np.array([len(r["tin"].get(t, ())) for t in range(N)], np.uint32)
+    r["tin_off"] = np.concatenate([[0], np.cumsum(r["tin_cnt"])[:-1]]).astype(np.uint32)
+    r["tlist"] = set(r["tin"])
+    r["rt0"] = {t: int(c["rtail"][t]) for t in r["tlist"]}
+    # ---- sends
+    r["new"], r["tag"], sends = {}, {}, 0
+    em = np.zeros(2 * N, np.int64)
+    dm = gs_bits(c["DM"])
+    r["rtail"] = c["rtail"].astype(np.int64)
+    window = []
+    for m in range(N):  # the window entries [rwin', rseen') in ring order
+        ring, a, n = gs_ring(c, m), (int(r["rwin"][m]) - int(c["rhead"][m])) & M32, (int(r["rseen"][m]) - int(r["rwin"][m])) & M32
+        window.append([(g, p) for _, g, p in ring[a:a + n]])
+        assert {g for g, _ in window[m]} == WB[m]
+    gs_contacts_ref(c, r, window, rows)
+    r["rp"], r["slow"] = [], []
+    for t in sorted(r["tlist"]):
+        new = set()
+        for ms in r["tin"][t]:
+            m, s = divmod(ms, F)
+            sent = set(WB[m])
+            if r["cin"][ms] != NEVER:
+                slow = r["cin"][ms] == 0xFFFFFFFE
+                wr = WB[m] & r["rx"][ms][2] if ms in r["rx"] else set(WB[m])
+                if wr:
+                    r["fb"][FB_CEV_SLOW if slow else FB_REPLAY] += len(wr)
+                    r["slow" if slow else "rp"] += [(g << 32) | ms for g in wr]
+                for g in wr:  # isInfected (:247): the explicit set if the case has one; else nobody who never held it
+                    if "infected" in c:
+                        sent -= {g} if t in c["infected"][m, g] else set()
+                    elif gs_s_get(c, int(c["S"][t][g]), g, k + lat) is not None:
+                        raise NotImplementedError("a replayed gossip its target held: the answer needs the pair's history")
+                sent -= {g for g in wr if (g << 32) | ms in dropped}
+            sends += len(sent)
+            pct = gs_pct(c, m, t)
+            if c["flags"] & GS_EM and k < c["dead_tick"][t]:  # a dead target refuses the connection: not counted
+                nl = len(gs_lost(c, m, s, sent, pct))
+                em[2 * m] += 2 * len(sent) - nl
+                em[2 * m + 1] += nl
+            cand = sent - HB[t]
+            new |= cand - gs_lost(c, m, s, cand, pct)
+        r["new"][t], r["tag"][t] = new, rounds_before(int(c["firstGossip"][t]), k + lat, c["gossip_t"]) & 1023
+        HB[t] |= new
+        r["rtail"][t] = (r["rt0"][t] + len(new)) & M32
+        if new & dm:
+            r["dead_rx"][t] = k + lat
+        if (r["rtail"][t] - r["rhead"][t]) & M32 > c["BCAP"]:
+            r["err"] |= E_RING
+    r["ctr_g"], r["em"], r["HB"], r["WB"] = sends, em, HB, WB
+    if len(r["rp"]) > c["RPCAP"] or len(r["slow"]) > c["SLOWCAP"]:
+        r["err"] |= E_CONTACTS
+    if not c["flags"] & GS_FB:
+        r["fb"][:] = 0
+    r["tin_cnt_send"] = r["tin_cnt"]
+    if not c["flags"] & GS_APPLY:
+        r["tin_fill"], r["S"] = r["tin_cnt"], S
+        return r
+    # ---- apply
+    r["tin_cnt"] = r["tin_fill"] = np.zeros(N, np.uint32)
+    routed, hist = [], {kk: list(v[1]) for kk, v in gs_hist_decode(c["hist"]).items()}
+    r["hist_old"] = set(hist)
+    for t in sorted(r["tlist"]):
+        for g in sorted(r["new"][t]):
+            prev = gs_s_get(c, int(S[t][g]), g, k + lat)
+            S[t][g] = S16_EVER | ((k + lat) & S16_TICK) | (S16_REBORN if prev is not None else 0)
+            if prev is not None:
+                hist.setdefault((int(c["slot_gid"][g]), t), []).append(prev)
+            r["slot_exp"][g] = k + lat + c["EXPB"]
+            subj, key = int(c["slot_subj"][g]), int(c["slot_key"][g])
+            if subj == USER_SUBJ:
+                route = True
+            else:
+                r0 = int(c["rowk"][t][subj])
+                route = (r0 & 3 == 0 or gs_overrides((key >> 32) & 3, key & M32, r0 & 3, r0 >> 2) or r["dead_rx"][t] == k + lat
+                         or bool(c["leaving"][subj]))
+            if route:
+                routed.append((t << 32) | g)
+            else:
+                r["rc_ndrop"][t] += 1
+        r["held"][t] += len(r["new"][t])
+    r["S"], r["routed"], r["hist"] = S, sorted(routed), {kk: (len(v), tuple(v)) for kk, v in hist.items()}
+    r["ap"] = {t for t in r["tlist"] if len(r["new"][t]) > APPLY_LANE}
+    if len(routed) > c["RCAP"]:
+        r["err"] |= E_RECEIPTS
+    # ---- expire and free
+    gone = sorted(g for g in gs_bits(c["GU"]) if r["slot_exp"][g] <= k)
+    if any(((k - int(c["slot_ctick"][g])) & M32) > SLIFE for g in gs_bits(c["GU"])):
+        r["err"] |= E_SLIFE
+    r["GU"], r["DM"] = gs_bits(c["GU"]) - set(gone), dm - set(gone)
+    r["slot_used"][gone] = 0
+    r["fexp"], r["free"] = gone, [g for g in gone if g // c["SPR"] == c["rank"]]
+    return r
+
+
+def gs_invariants(c):
+    """The conditions a state of the engine meets between ticks; a list of the violations."""
+    bad, used = [], gs_bits(c["GU"])
+    for g in range(c["SLOTS"]):
+        if c["slot_used"][g] and g not in used:
+            bad.append(("used slot without its GU bit", g))
+    if not gs_bits(c["DM"]) <= used:
+        bad.append("DM bit of a free slot")
+    for m in range(c["N"]):
+        ring = gs_ring(c, m, rounds_before(int(c["firstGossip"][m]), c["k"], c["gossip_t"]))
+        slots, per = [s for _, s, _ in ring], [p for _, _, p in ring]
+        h, n = int(c["rhead"][m]), len(ring)
+        w, s = (int(c["rwin"][m]) - h) & M32, (int(c["rseen"][m]) - h) & M32
+        if n > c["BCAP"] or not w <= s <= n:
+            bad.append(("ring positions", m))
+            continue
+        if per != sorted(per):
+            bad.append(("ring periods decrease", m))
+        if len(set(slots)) != n or not set(slots) <= used:
+            bad.append(("ring slots repeat or are free", m))
+        if gs_bits(c["HB"][m]) != set(slots):
+            bad.append(("HB is not the ring's slots", m))
+        if gs_bits(c["WB"][m]) != set(slots[w:s]):
+            bad.append(("WB is not the slots of [rwin, rseen)", m))
+        if c["held"][m] != n:
+            bad.append(("held", m))
+        if any(not c["S"][m][g] & S16_EVER or c["S"][m][g] & S16_SWEPT for g in slots):
+            bad.append(("S entry of a held slot", m))
+        if c["tround"][m] and (c["tcnt"][m] > c["F"] or any(t >= c["N"] or t == m for t in c["T"][m][:c["tcnt"][m]])):
+            bad.append(("round targets", m))
+        ticks = sorted(int(t) for t in c["log_tick"][m] if t != NEVER)
+        if any(b - a < c["gossip_t"] for a, b in zip(ticks, ticks[1:])) or (ticks and ticks[-1] >= c["k"]):
+            bad.append(("log ticks closer than a gossip interval", m))
+    return bad
+
+
+# ---- case builders (fixed seeds; test_prim_ref.py checks every one against gs_invariants)
+GS_GROUP_QWS = [1, 2, 64, 1024, 1025, 2049]  # one scan batch, its last thread, a second batch, a third with one word
+GS_GROUP_KINDS = ["empty", "full", "last", "every7"]
+
+
+def gs_group_case(QW, kind):
+    """One member, no rings: only the group words matter (and the counters k_gossip_groups resets)."""
+    c = gs_new(1, 64 * QW)
+    words = {"empty": [], "full": range(QW), "last": [QW - 1], "every7": range(0, QW, 7)}[kind]
+    for q in words:
+        c["GU"][q] = M64 if kind == "full" else 1 << (q % 64)
+    c["slot_used"][sorted(gs_bits(c["GU"]))] = 1
+    return c
+
+
+def _gs_fill(c, m, periods, slots, gid0=1 << 40):
+    for g, p in zip(slots, periods):
+        if not c["slot_used"][g]:
+            gs_use(c, g, gid0 + g)
+        gs_hold(c, m, g, p)
+
+
+def gs_prev_window(c, m, Pprev, sp_prev, nnew):
+    """m's window as its previous round (period Pprev, spread sp_prev) left it; the last nnew entries arrived since."""
+    ring = gs_ring(c, m, Pprev)
+    gs_seen(c, m, sum(1 for _, _, p in ring[:len(ring) - nnew] if p < Pprev - sp_prev), len(ring) - nnew)
+
+
+def gs_rounds_edges():
+    """Round members at every boundary of the sweep and the window (spread 2: swept below P - 6, window from P - 2), for
+    periods on both sides of the 10-bit tag wrap; rings that cross a multiple of BCAP and 2^32; a spread that grew and one
+    that shrank since the previous round; a round with nothing to do; a completed leave. 5-word rows, the last one active."""
+    c = gs_new(12, 320, BCAP=64)
+    m, free = 0, iter(range(320))
+    for P in (5, 1023, 1024, 1030, 3071):
+        sp = 2
+        per = [p for p in (P - 9, P - 8, P - 7, P - 6, P - 5, P - 3, P - 2, P - 1, P, P) if p >= 0]
+        c["rhead"][m] = c["rtail"][m] = (60, 0xFFFFFFF0, 0, 7, 0xFFFFFFFF)[m]
+        _gs_fill(c, m, per, [next(free) for _ in per])
+        gs_round(c, m, P, sp)
+        gs_prev_window(c, m, P - 1, sp, 2)
+        m += 1
+    # the spread grew from 1 to 4 (entries re-enter the window), and shrank from 4 to 1
+    for sp0, sp1 in ((1, 4), (4, 1)):
+        P = 2000
+        per = [P - 12, P - 7, P - 5, P - 4, P - 3, P - 2, P - 1, P - 1]
+        _gs_fill(c, m, per, [next(free) for _ in per])
+        gs_round(c, m, P, sp1)
+        gs_prev_window(c, m, P - 1, sp0, 1)
+        m += 1
+    # nothing to do: the previous round was this very plan and nothing arrived (not listed, nothing moves)
+    P = 700
+    _gs_fill(c, m, [P - 6, P - 2, P - 1], [next(free) for _ in range(3)])
+    gs_round(c, m, P, 2)
+    gs_prev_window(c, m, P, 2, 0)
+    idle = m
+    m += 1
+    # the leave completion: the swept entry is m's own DEAD record
+    g = next(free)
+    gs_use(c, g, (m << 32) | 5, subj=m, key=(ST_DEAD << 32) | 3)
+    _gs_fill(c, m, [10, 30], [g, next(free)])
+    gs_round(c, m, 30, 2)
+    gs_prev_window(c, m, 29, 2, 0)
+    leaver = m
+    m += 1
+    # a member without a round whose ring looks like work (not touched), and one holding the last slot (the span)
+    _gs_fill(c, m, [1, 2, 3], [next(free) for _ in range(3)])
+    c["firstGossip"][m] = c["k"] - 40 * c["gossip_t"]
+    gs_seen(c, m, 0, 1)
+    m += 1
+    _gs_fill(c, m, [8, 9], [318, 319])
+    gs_round(c, m, 9, 3)
+    gs_prev_window(c, m, 8, 3, 1)
+    c["idle"], c["leaver"] = idle, leaver
+    return c
+
+
+GS_SWEEP_NS = [1, 63, 64, 65, 255, 256, 257, 1025]
+
+
+def gs_rounds_sweeps():
+    """Member i sweeps GS_SWEEP_NS[i] entries and keeps 3 (ring_walk's four-deep unroll and remainder, on 64 and on 256
+    threads); 17-word rows. The rings start just below 2^32."""
+    c = gs_new(len(GS_SWEEP_NS), 64 * 17, BCAP=2048)
+    for g in range(c["SLOTS"]):
+        gs_use(c, g, (9 << 32) | g)
+    rng = np.random.default_rng(77)
+    for m, n in enumerate(GS_SWEEP_NS):
+        P = 900 + m
+        c["rhead"][m] = c["rtail"][m] = (0xFFFFFC00 + 37 * m) & M32
+        slots = rng.permutation(c["SLOTS"])[:n + 3].tolist()
+        _gs_fill(c, m, [P - 30] * n + [P - 4, P - 1, P], slots)
+        gs_round(c, m, P, 2)
+        gs_prev_window(c, m, P - 20, 2, 1)  # the swept entries were in the window then
+    return c
+
+
+def gs_rounds_empty():
+    """span = 0: no slot in use, round members with empty rings."""
+    c = gs_new(3, 320)
+    gs_round(c, 0, 10, 2)
+    gs_round(c, 2, 11, 2)
+    return c
+
+
+def gs_scatter_case():
+    """600 members (block_reserve crosses workgroups), F = 8: target 7 has 40 senders, 9 two, 11 one whose send is slot 7 of
+    a full round; members with fewer targets than F, with an empty round and without a round."""
+    c = gs_new(600, 64)
+    rng = np.random.default_rng(5)
+    for m in range(100, 140):
+        gs_round(c, m, 50, 2, [7] + rng.choice(np.arange(300, 600), int(rng.integers(0, 4)), replace=False).tolist())
+    gs_round(c, 20, 50, 2, [9])
+    gs_round(c, 21, 50, 2, [250, 9, 251])
+    gs_round(c, 22, 50, 2, [252, 253, 254, 255, 256, 257, 258, 11])
+    gs_round(c, 23, 50, 2, [])
+    for m in range(300, 600, 3):
+        gs_round(c, m, 50, 2, rng.choice(np.arange(0, 100), int(rng.integers(1, 8)), replace=False).tolist())
+    return c
+
+
+def gs_send_case(nag, ntl, seed, QW=None, hold=0.5, BCAP=1024, **kw):
+    """ntl targets with 1..3 senders each over nag active groups; every member has a round, holds about `hold` of the
+    gossips (so windows overlap and targets hold some), a dead target, DEAD membership records among the gossips."""
+    rng = np.random.default_rng(seed)
+    QW = QW or (nag + 2 if nag > 1 else 1)
+    N = ntl + 4
+    c = gs_new(N, 64 * QW, BCAP=BCAP, **kw)
+    c["rowk"] = rng.integers(0, 16, (N, (N + 7) & ~7)).astype(np.uint32)  # status | inc << 2
+    groups = sorted(rng.choice(QW - 1, nag - 1, replace=False).tolist() + [QW - 1]) if nag > 1 else [0]
+    slots = []
+    for i, q in enumerate(groups):
+        bits = range(64) if i == 0 else rng.choice(64, int(rng.integers(1, 5)), replace=False).tolist()
+        slots += [q * 64 + b for b in bits]
+    for g in slots:
+        kind = rng.integers(0, 4)
+        subj = USER_SUBJ if kind == 0 else int(rng.integers(0, N))
+        key = int(rng.integers(0, 2**32)) | int(rng.integers(0, 2**32)) << 32 if kind == 0 else \
+            (int(rng.integers(1, 4)) << 32) | int(rng.integers(0, 4))
+        gs_use(c, g, int(rng.integers(1, 2**63)), subj, key, ctick=c["k"] - int(rng.integers(5, 30)))
+    c["leaving"][rng.choice(N, 2, replace=False)] = 1
+    c["ep_group"][:] = np.arange(N) % 2
+    cap = [c["F"]] * N
+    targets = [[] for _ in range(N)]
+    for t in range(ntl):
+        want = 1 + t % 3
+        for m in rng.permutation(N).tolist():
+            if want and m != t and cap[m] and t not in targets[m]:
+                targets[m].append(t)
+                cap[m] -= 1
+                want -= 1
+        assert want == 0
+    for m in range(N):
+        P, sp = 300 + 7 * m, 2 + m % 3
+        mine = [g for g in slots if rng.random() < hold]
+        rng.shuffle(mine)
+        per = sorted(int(P - min(rng.integers(0, 2 * sp + 2), rng.integers(0, 2 * sp + 6))) for _ in mine)
+        c["rhead"][m] = c["rtail"][m] = int(rng.integers(0, 2**32))
+        for g, p in zip(mine, per):
+            gs_hold(c, m, g, p, ctick=max(int(c["slot_ctick"][g]), c["k"] - 2 * (P - p) - 1))
+        gs_round(c, m, P, sp, targets[m])
+        gs_prev_window(c, m, P - 1, sp, min(len(mine), int(rng.integers(0, 3))))
+        # entries of earlier incarnations and of the slots' earlier gossips in the rows of S the apply reads
+        for g in rng.choice(slots, min(len(slots), 12), replace=False).tolist():
+            if g not in mine:
+                old = rng.random() < 0.5
+                tick = int(c["slot_ctick"][g]) - 3 if old else int(c["slot_ctick"][g]) + 1
+                c["S"][m][g] = S16_EVER | S16_SWEPT | (tick & S16_TICK)
+    c["dead_tick"][ntl // 2] = c["k"] - 3
+    c["targets"] = ntl
+    return c
+
+
+GS_SEND_SHAPES = {"nag1": (1, 70), "nag3": (3, 30), "nag64": (64, 3), "nag65": (65, 3)}
+
+
+def gs_apply_case(RCAP=None, slife=False):
+    """Targets 0..6 gain 0, 1, 8, 9, 64, 65 and 4096 + 65 entries from one lossless sender each (member 7 + i); gossips of
+    every routing kind, rebirths and stale S entries, slots that expire at k - 1, k, k + 1, in and out of rank 1's range."""
+    gains = [0, 1, 8, 9, 64, 65, 4096 + 65]
+    rng = np.random.default_rng(99)
+    N, SLOTS = 14, 64 * 70
+    c = gs_new(N, SLOTS, BCAP=8192, flags=GS_APPLY, RCAP=RCAP or 8192, sort_cap=64, rank=1, SPR=SLOTS // 2, free_top=3, HCAP=4096,
+               lat=1, EXPB=40)
+    c["rowk"] = rng.integers(0, 16, (N, 16)).astype(np.uint32)
+    c["rowk"][:, ::2] |= 3  # every other subject DEAD in every row: no record overrides it
+    c["leaving"][[2, 9]] = 1
+    pool = rng.permutation([g for g in range(64, SLOTS) if not 2240 <= g < 2245]).tolist()  # the others: the expiry slots
+    for i, n in enumerate(gains):
+        t, m = i, 7 + i
+        P = 400 + i
+        own = [pool.pop() for _ in range(n)]
+        both = [pool.pop() for _ in range(3)]  # held by the target too: no receipt
+        for g in own + both:
+            kind = rng.integers(0, 3)
+            subj = USER_SUBJ if kind == 0 else int(rng.integers(0, N))
+            # DEAD records (their receipt stamps dead_rx: every receipt of the target is routed) only to target 5
+            key = int(rng.integers(0, 2**63)) if kind == 0 else (int(rng.integers(1, 4 if i == 5 else 3)) << 32) | int(rng.integers(0, 4))
+            gs_use(c, g, int(rng.integers(1, 2**63)), subj, key, ctick=c["k"] - 50)
+        c["rhead"][m] = c["rtail"][m] = int(rng.integers(0, 2**32))
+        for g in own + both:
+            gs_hold(c, m, g, P - 1)
+        gs_round(c, m, P, 2, [t])
+        gs_prev_window(c, m, P - 1, 2, 0)
+        c["rhead"][t] = c["rtail"][t] = (0xFFFFFFF8, 5, 8190, 0, 77, 8100, 4000)[i]
+        for g in both:
+            gs_hold(c, t, g, 100)
+        c["firstGossip"][t] = c["k"] - 102 * c["gossip_t"]
+        gs_seen(c, t, 0, 3)
+        for j, g in enumerate(own):  # a third swept this gossip before (a rebirth), a third an earlier gossip of the slot
+            if j % 3 == 0:
+                c["S"][t][g] = S16_EVER | S16_SWEPT | ((c["k"] - 30 - j % 7) & S16_TICK)
+            elif j % 3 == 1:
+                c["S"][t][g] = S16_EVER | S16_SWEPT | ((c["k"] - 51 - j % 5) & S16_TICK)
+    for j, (g, e) in enumerate([(1, -1), (2, 0), (3, 1), (40, -1), (41, 0), (63, 5)]):
+        gs_use(c, g, (77 << 32) | g, subj=3 if j == 1 else USER_SUBJ, key=(ST_DEAD << 32) | 1 if j == 1 else 7,
+               ctick=c["k"] - SLIFE - (1 if slife and j == 5 else 0), exp=c["k"] + e)
+    for g, e in ((2240, -1), (2241, 0), (2242, 1), (2244, -7)):  # rank 1's range starts at SLOTS / 2 = 2240
+        gs_use(c, g, (78 << 32) | g, exp=c["k"] + e)
+    c["free_list"][:3] = [9001, 9002, 9003]
+    c["gains"] = gains
+    return c
+
+
+def gs_log(c, x, rounds, pos=None):
+    """Member x's round log: rounds = [(tick, spread, targets)] oldest first, the newest at ring index (log_pos - 1)."""
+    L = c["LOGW"]
+    pos = len(rounds) if pos is None else pos
+    assert len(rounds) <= L and pos >= len(rounds) and (pos <= L or len(rounds) == L)
+    c["log_pos"][x] = pos
+    for i, (tick, sp, tg) in enumerate(rounds):
+        e = (pos - len(rounds) + i) & (L - 1)
+        c["log_tick"][x][e], c["log_spread"][x][e], c["log_cnt"][x][e] = tick, sp, len(tg)
+        c["log_tg"][x][e][:len(tg)] = tg
+
+
+def gs_contact_case(LOGW=8, **kw):
+    """Pairs (sender 2 i, target 2 i + 1) with logged contacts around the look-back cut k - (spread + 1) gossip_t - lat = k - 7
+    (spread 2, gossip_t 2, lat 1). Every sender's window holds periods P - 2, P - 2, P - 1, P, P (and an entry out of the
+    window); no target ever held a gossip of its sender, so each replayed gossip is sent (situation (c))."""
+    c = gs_new(18, 192, LOGW=LOGW, BCAP=64, flags=GS_FB, **kw)
+    k, free = c["k"], iter([g for g in range(192) if not 64 <= g < 128])  # group 1 stays empty
+    P, sp = 1200, 2
+    filler = lambda ticks: [(t2, 2, [17]) for t2 in ticks]  # rounds that target somebody else
+    def pair(i, per, tlog, mlog=(), tpos=None, mpos=None):
+        m, t = 2 * i, 2 * i + 1
+        _gs_fill(c, m, per, [next(free) for _ in per])
+        gs_round(c, m, P, sp, [16, t] if i % 2 else [t])
+        gs_prev_window(c, m, P - 1, sp, 1)
+        _gs_fill(c, t, [40, 41], [next(free) for _ in range(2)])
+        c["firstGossip"][t] = k - 2 * 60 - 1  # t's rounds fall on the other parity
+        gs_seen(c, t, 0, 2)
+        gs_log(c, t, tlog, tpos)
+        if mlog:
+            gs_log(c, m, mlog, mpos)
+    full = [P - 5, P - 2, P - 2, P - 1, P, P]
+    pair(0, full, [(k - 9, 2, [0]), (k - 7, 2, [0])] + filler([k - 5, k - 3, k - 1]))      # exactly at the cut: no contact
+    pair(1, full, filler([k - 8]) + [(k - 6, 2, [16, 2])] + filler([k - 4, k - 2]))        # one tick after it: a split window
+    pair(2, full, filler([k - 6, k - 4]) + [(k - 2, 3, [4])])                              # the whole window is older
+    pair(3, [P - 5, P - 1, P, P], [(k - 6, 2, [6])] + filler([k - 4, k - 2]))              # every window gossip is newer
+    pair(4, full, [(k - 6, 2, [8]), (k - 4, 2, [8]), (k - 2, 2, [17, 8])],                 # CEV events
+         [(k - 5, 2, [9]), (k - 3, 2, [9]), (k - 1, 2, [9])])
+    pair(5, full, [(k - 8, 2, [10]), (k - 6, 2, [10]), (k - 4, 2, [10]), (k - 2, 2, [10])],  # CEV + 1: the slow path
+         [(k - 5, 2, [11]), (k - 3, 2, [11]), (k - 1, 2, [11])])
+    pair(6, full, filler([k - 8]) + [(k - 6, 4, [12])] + filler([k - 4, k - 2]))           # a second split window
+    # a wrapped log, the contact in target slot 7 of a full round; with LOGW > 64 it lies in the second 64 entries
+    ticks = [k - 2 * (LOGW - j) for j in range(LOGW)]
+    pair(7, full, [(t2, 2, [17, 16, 15, 13, 12, 11, 10, 14] if t2 == k - 6 else [17]) for t2 in ticks], tpos=LOGW + (70 if LOGW > 64 else 3))
+    c["ep_group"][:] = (np.arange(18) // 2) % 2  # pairs share a side, except through the partition variant's members
+    return c
+
+
+class GsSim:
+    """A tiny forward simulation of GossipProtocolImpl with explicit infectedFrom sets (two to four members, scripted
+    rounds, lossless links or, across the two sides of a partition, fully blocked ones). It keeps what the reference keeps:
+    per member the held gossips with their infection period and `infected` set, and writes down as it goes what the engine
+    keeps instead: receipt rings, round logs, holder-table entries, the incarnation history. encode() gives the device
+    state at tick k together with the explicit sets, so a case carries both the encoding and the answer."""
+
+    def __init__(self, N, gossip_t=2, lat=1, side=None):
+        self.N, self.gt, self.lat, self.side = N, gossip_t, lat, side or [0] * N
+        self.held = [dict() for _ in range(N)]      # g -> dict(ctick, infp, infected, reborn)
+        self.ring = [[] for _ in range(N)]          # (g, infp) in receipt order
+        self.swept = [0] * N                        # entries swept so far: the ring's absolute head
+        self.win = [(0, 0)] * N                     # absolute (rwin, rseen) as the member's latest round left them
+        self.log = [[] for _ in range(N)]
+        self.last = [dict() for _ in range(N)]      # g -> (ctick, reborn) of the latest incarnation, swept or not
+        self.hist, self.born, self.due = {}, {}, []
+
+    def rb(self, x, tick):
+        return rounds_before(0, tick, self.gt)  # every member's first round is at tick 0
+
+    def _arrive(self, now):
+        for at, x, y, g in [d for d in self.due if d[0] <= now]:
+            if g in self.held[y]:
+                self.held[y][g]["infected"].add(x)  # onGossipReq (:171-183): a known gossip only notes the sender
+            else:
+                reborn = g in self.last[y]
+                if reborn:
+                    self.hist.setdefault((g, y), []).append(self.last[y][g][0])
+                self.held[y][g] = dict(ctick=at, infp=self.rb(y, at), infected={x}, reborn=reborn)
+                self.last[y][g] = (at, reborn)
+                self.ring[y].append((g, self.rb(y, at)))
+        self.due = [d for d in self.due if d[0] > now]
+
+    def create(self, x, g, tick):
+        self._arrive(tick)
+        self.born[g] = (x, tick)
+        self.held[x][g] = dict(ctick=tick, infp=self.rb(x, tick), infected=set(), reborn=False)
+        self.last[x][g] = (tick, False)
+        self.ring[x].append((g, self.rb(x, tick)))
+
+    def round(self, x, tick, targets, sp):
+        """doSpreadGossip (:139-157) of x at `tick`: the sweep, then to each target the window gossips it is not infected by."""
+        assert tick % self.gt == 0
+        self._arrive(tick)
+        P = self.rb(x, tick)
+        gone = [g for g, st in self.held[x].items() if st["infp"] + 2 * (sp + 1) < P]
+        for g in gone:
+            del self.held[x][g]
+        self.swept[x] += len(gone)
+        self.ring[x] = [(g, p) for g, p in self.ring[x] if g not in gone]
+        for y in targets:
+            for g, st in self.held[x].items():
+                if st["infp"] + sp >= P and y not in st["infected"] and self.side[x] == self.side[y]:
+                    self.due.append((tick + self.lat, x, y, g))
+        self.log[x].append((tick, sp, list(targets)))
+        inwin = sum(1 for _, p in self.ring[x] if p + sp < P)
+        self.win[x] = (self.swept[x] + inwin, self.swept[x] + len(self.ring[x]))
+
+    def encode(self, k, rounds, LOGW=16, **kw):
+        """The state at tick k before its rounds {m: (targets, spread)}; c["infected"][m, g] is infectedFrom_m(g)."""
+        self._arrive(k)
+        c = gs_new(self.N, 64, k=k, LOGW=LOGW, BCAP=16, gossip_t=self.gt, lat=self.lat, flags=GS_FB | GS_APPLY, HCAP=64,
+                   ep_part=int(len(set(self.side)) > 1), **kw)
+        c["ep_group"][:] = self.side
+        c["firstGossip"][:] = 0
+        for g, (x, tick) in self.born.items():
+            gs_use(c, g, (x << 32) | (g + 1), ctick=tick, exp=k + 100)
+        for x in range(self.N):
+            c["rhead"][x] = c["rtail"][x] = self.swept[x]
+            for g, p in self.ring[x]:
+                gs_hold(c, x, g, p)
+            for g, (ctick, reborn) in self.last[x].items():
+                c["S"][x][g] = S16_EVER | (ctick & S16_TICK) | (S16_REBORN if reborn else 0) | (0 if g in self.held[x] else S16_SWEPT)
+            c["rwin"][x], c["rseen"][x] = self.win[x]
+            w, s = self.win[x][0] - self.swept[x], self.win[x][1] - self.swept[x]
+            c["WB"][x] = gs_words([g for g, _ in self.ring[x][max(w, 0):s]], 1)
+            gs_log(c, x, self.log[x][-LOGW:], len(self.log[x]))
+        for (g, x), ticks in self.hist.items():  # hist_push's table: linear probing from the tag
+            gid = int(c["slot_gid"][g])
+            tag, n = gs_hist_tag(gid, x), len(ticks)
+            i = next((tag + p) & 63 for p in range(64) if c["hist"][(tag + p) & 63][0] == 0)
+            c["hist"][i][:3] = [tag, gid, x | n << 32]
+            c["hist"][i][3:].view(np.uint32)[:n] = ticks
+        for m, (targets, sp) in rounds.items():
+            c["tround"][m], c["tperiod"][m], c["tspread"][m], c["tcnt"][m] = 1, self.rb(m, k), sp, len(targets)
+            c["T"][m][:len(targets)] = targets
+        c["infected"] = {(x, g): set(st["infected"]) for x in range(self.N) for g, st in self.held[x].items()}
+        return c
+
+
+def gs_replay_cases():
+    """The canonical infectedFrom situations. Members: m = 0 sends to t = 1 at tick k; u = 2 (a long spread) and v = 3 help.
+    gossip_t 2, lat 1, m and t spread 1 (window P - 1, swept below P - 4)."""
+    cs = {}
+    # (a) t delivered g0 to m inside m's current incarnation: not sent back. (c) g1, which t never held: sent.
+    # (e) g2, created after the contact arrived: not even replayed. m -> t at k - 2 makes a second contact event.
+    def sim_a():
+        s = GsSim(3)
+        for tick in range(2, 20, 2):
+            s.round(2, tick, [], 1)
+        s.create(1, 0, 16)
+        s.round(1, 16, [0], 1)
+        s.round(0, 18, [2, 1], 1)
+        s.round(1, 18, [], 1)
+        s.create(0, 1, 18)
+        s.create(0, 2, 19)
+        return s
+    cs["replay_a_c_e"] = sim_a().encode(20, {0: ([1], 1)})
+    cs["replay_d_slow"] = sim_a().encode(20, {0: ([1], 1)}, cev_cap=1)  # (d) the same through the full log scan
+    # (b) t delivered g0 to m long ago; m swept it and got it again from u; t's recent round reached m without g0: sent.
+    # (f) the same, but t got g0 again too (from v: u has t in its own infectedFrom) and sent it to m inside m's new
+    # incarnation: not sent.
+    for name, again in (("replay_b_older", False), ("replay_f_rebirth", True)):
+        s = GsSim(4)
+        s.create(1, 0, 2)
+        for tick in range(2, 20, 2):
+            s.round(1, tick, [0, 2] if tick == 2 else [0] if tick == 18 else [], 1)
+            s.round(0, tick, [], 1)
+            s.round(2, tick, [3] if tick == 4 else [0] if tick == 16 else [], 6)
+            s.round(3, tick, [1] if tick == 16 and again else [], 6)
+        cs[name] = s.encode(20, {0: ([1], 1), 3: ([2], 6)})
+    return cs
+
+
+def gs_cases():
+    """name -> state: every case of tests/test_gpu_gossip.py (one launch each)."""
+    cs = {}
+    for QW in GS_GROUP_QWS:
+        for kind in GS_GROUP_KINDS:
+            cs[f"groups_{QW}_{kind}"] = gs_group_case(QW, kind)
+    for base, c in (("edges", gs_rounds_edges()), ("sweeps", gs_rounds_sweeps()), ("empty", gs_rounds_empty())):
+        for path, kw in GS_PATHS.items():
+            cs[f"rounds_{base}_{path}"] = gs_variant(c, **kw)
+    cs["scatter"] = gs_scatter_case()
+    for name, (nag, ntl) in GS_SEND_SHAPES.items():
+        cs[f"send_{name}"] = gs_send_case(nag, ntl, 11)
+    # 2049-word rows: the workgroup path at the engine's own chunk sizes, and the third batch of the group scan
+    cs["send_nag130"] = gs_send_case(130, 2, 12, QW=2049, hold=0.7)
+    cs["send_loss37"] = gs_variant(cs["send_nag3"], ep_loss=37)
+    cs["send_loss100"] = gs_variant(cs["send_nag3"], ep_loss=100)
+    cs["send_partition"] = gs_variant(cs["send_nag3"], ep_part=1)
+    cs["send_ring_full"] = gs_send_case(3, 30, 11, BCAP=64)
+    for name in list(GS_SEND_SHAPES) + ["nag130", "loss37"]:
+        cs[f"send_{name}_em"] = gs_variant(cs[f"send_{name}"], flags=GS_EM)
+    cs["contacts"] = gs_contact_case()
+    cs["contacts_logw128"] = gs_contact_case(LOGW=128)
+    cs["contacts_cev1"] = gs_variant(cs["contacts"], cev_cap=1)
+    cs["contacts_crcap1"] = gs_variant(cs["contacts"], CRCAP=1)
+    cs["contacts_rpcap_short"] = gs_variant(cs["contacts"], RPCAP=len(gs_ref(cs["contacts"])["rp"]) - 1)
+    cs["contacts_loss37"] = gs_variant(cs["contacts"], ep_loss=37, flags=GS_FB | GS_EM)
+    cs["contacts_cx1"] = gs_variant(cs["contacts"], cx=1, flags=GS_FB | GS_APPLY)  # RX rows staged in three chunks
+    cs["contacts_cx2"] = gs_variant(cs["contacts"], cx=2)  # in two, the last one partial
+    cs.update(gs_replay_cases())
+    cs["apply_nag3"] = gs_variant(cs["send_nag3"], flags=GS_APPLY)
+    cs["apply_loss37"] = gs_variant(cs["send_loss37"], flags=GS_APPLY | GS_FB)
+    cs["apply_gains"] = gs_apply_case()
+    cs["apply_rcap_short"] = gs_apply_case(RCAP=len(gs_ref(cs["apply_gains"])["routed"]) - 1)
+    cs["apply_slife"] = gs_apply_case(slife=True)
+    return cs

@@ -17,33 +17,13 @@ The oracle cannot hold 10^6 members, so these tests check size-independent prope
 import numpy as np
 import pytest
 
+from prim_ref import mix64, philox
 from swimhip import SimConfig, _abi
 from swimhip.cluster import SimulatedCluster
 
 pytestmark = pytest.mark.gpu
 
-M32 = np.uint64(0xFFFFFFFF)
 SALT_CHURN = 0x43485552
-
-
-def philox(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 over numpy arrays (swim_common.h philox)."""
-    c = [np.asarray(x, dtype=np.uint64) & M32 for x in (c0, c1, c2, c3)]
-    k0, k1 = np.uint64(k0), np.uint64(k1)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & M32, p1 & M32, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & M32, p0 & M32]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M32
-    return c
-
-
-def mix64(z):
-    z = (z + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
-    return z ^ (z >> 31)
 
 
 def test_philox_restatement_known_answers():

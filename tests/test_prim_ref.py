@@ -726,3 +726,179 @@ def test_exchange_calls_are_well_formed():
         params, inp, out = R.xu_pack(c)
         assert len(params) == 18 and inp.ctypes.data % 8 == 0 and out.ctypes.data % 8 == 0 and (out == R.XP_BYTE).all()
         assert R.xu_unpack(c, out)["sc"]["err"] == R.XP_WORD
+
+
+# ---------------------------------------------------------------------------------------------- gossip data plane
+GS = R.gs_cases()
+
+
+def test_gs_period_is_the_nearest_period_with_that_tag():
+    for P in (0, 5, 511, 512, 1023, 1024, 1030, 3071, 10**6):
+        for tag in range(1024):
+            near = [p for p in range(P - 512, P + 512) if p & 1023 == tag]
+            assert near == [R.gs_period(tag, P)], (P, tag)
+
+
+@pytest.mark.parametrize("name", list(GS))
+def test_gs_case_meets_the_engine_invariants(name):
+    assert R.gs_invariants(GS[name]) == [], name
+
+
+@pytest.mark.parametrize("name", list(GS))
+def test_gs_round_reference_against_the_range_formulation(name):
+    """Classifying every ring entry on its own against searching the sorted periods for the two boundaries."""
+    c = GS[name]
+    listed = 0
+    for m in range(c["N"]):
+        a, b = R.gs_round_ref(c, m), R.gs_round_ref_ranges(c, m)
+        assert a == b, (name, m)
+        listed += a is not None
+    if name.startswith(("rounds_edges", "rounds_sweeps", "send_", "contacts")):
+        assert listed, name
+
+
+def test_gs_round_cases_hold_the_boundaries_they_name():
+    c = R.gs_rounds_edges()
+    assert R.gs_round_ref(c, c["idle"]) is None and R.gs_ref(c)["dead_tick"][c["leaver"]] == c["k"] + 1
+    for m in range(5):  # an entry at, one below and one above both boundaries
+        P, sp = int(c["tperiod"][m]), int(c["tspread"][m])
+        per = {p for _, _, p in R.gs_ring(c, m)}
+        want = {P - 2 * (sp + 1) + d for d in (-1, 0, 1)} | {P - sp + d for d in (-1, 0, 1)}
+        assert {p for p in want if p >= 0} <= per, (m, sorted(per))
+    tags = lambda m: {int(e) >> 22 for e in c["rg"][m] if e != R.GS_SENT}
+    assert any({1023, 0} <= tags(m) for m in range(5)), "a ring with entries on both sides of the tag wrap"
+    assert any(int(c["rhead"][m]) > int(c["rtail"][m]) for m in range(c["N"])), "a ring across 2^32"
+    assert any(int(c["rhead"][m]) // c["BCAP"] != (int(c["rtail"][m]) - 1) // c["BCAP"] for m in range(c["N"]) if c["rtail"][m] > c["rhead"][m])
+    grown = [m for m in range(c["N"]) if R.gs_round_ref(c, m) and ((R.gs_round_ref(c, m)["wnew"] - int(c["rwin"][m])) & R.M32) >> 31]
+    assert grown, "a window that starts earlier than at the previous round (the spread grew)"
+    s = R.gs_rounds_sweeps()
+    assert [len(R.gs_round_ref(s, m)["swept"]) for m in range(s["N"])] == R.GS_SWEEP_NS
+
+
+@pytest.mark.parametrize("name", [n for n in GS if n.startswith(("scatter", "send_nag", "contacts"))])
+def test_gs_scatter_reference_by_sorting_the_pairs(name):
+    c, r = GS[name], R.gs_ref(GS[name])
+    pairs = sorted((int(c["T"][m][s]), m * c["F"] + s) for m in range(c["N"]) if c["tround"][m] for s in range(int(c["tcnt"][m])))
+    flat = [ms for _, ms in pairs]
+    for t in range(c["N"]):
+        o, n = int(r["tin_off"][t]), int(r["tin_cnt"][t]) if not c["flags"] & R.GS_APPLY else int(r["tin_cnt_send"][t])
+        assert flat[o:o + n] == r["tin"].get(t, []) and all(p[0] == t for p in pairs[o:o + n]), (name, t)
+    assert sum(len(v) for v in r["tin"].values()) == len(pairs)
+
+
+def _words(slots, QW):
+    return [int(x) for x in R.gs_words(slots, QW)]
+
+
+@pytest.mark.parametrize("name", [n for n in GS if n.startswith("send_")])
+def test_gs_send_reference_against_word_arithmetic(name):
+    """gs_ref decides one gossip at a time; here a target's receipts are built 64 slots at a time: window word & ~held word,
+    minus the word of lost draws, OR-ed over the senders."""
+    c, r = GS[name], R.gs_ref(GS[name])
+    QW, F = c["SLOTS"] // 64, c["F"]
+    for t, senders in r["tin"].items():
+        held = _words(r["HB"][t] - r["new"][t], QW)
+        got = [0] * QW
+        for ms in senders:
+            m, s = divmod(ms, F)
+            win, pct = _words(r["WB"][m], QW), R.gs_pct(c, m, t)
+            for q in range(QW):
+                cand = win[q] & ~held[q] & R.M64
+                lost = 0
+                for b in range(64):
+                    if cand >> b & 1 and (pct >= 100 or (pct > 0 and R.gs_lost(c, m, s, [q * 64 + b], pct))):
+                        lost |= 1 << b
+                got[q] |= cand & ~lost
+        assert R.gs_bits(np.array(got, np.uint64)) == r["new"][t], (name, t)
+    assert r["ctr_g"] == sum(len(r["WB"][ms // F]) for v in r["tin"].values() for ms in v)
+
+
+def test_gs_send_cases_hold_the_shapes_they_name():
+    twice = 0  # cases with a receipt that two senders of the target deliver
+    for name, (nag, ntl) in list(R.GS_SEND_SHAPES.items()) + [("nag130", (130, 2))]:
+        r = R.gs_ref(GS[f"send_{name}"])
+        assert (r["nag"], len(r["tlist"])) == (nag, ntl), name
+        assert nag == 64 or (nag * ntl) % 64, name
+        if nag not in (1, 64):  # some target's items lie on both sides of a wave boundary
+            assert any((i * nag) // 64 != ((i + 1) * nag - 1) // 64 for i in range(ntl)), name
+        assert len({len(v) for v in r["tin"].values()}) > 1, "uneven sender counts"
+        twice += any(len(v) > 1 and sum(len(r["WB"][ms // 8] & r["new"][t]) for ms in v) > len(r["new"][t]) for t, v in r["tin"].items())
+        assert r["dead_rx"].max() == GS[f"send_{name}"]["k"] + 1, "a DEAD record delivered"
+    assert twice >= 3
+    assert R.gs_ref(GS["send_ring_full"])["err"] == R.E_RING
+    assert 0 < sum(len(v) for v in R.gs_ref(GS["send_loss37"])["new"].values()) < sum(len(v) for v in R.gs_ref(GS["send_nag3"])["new"].values())
+    assert sum(len(v) for v in R.gs_ref(GS["send_loss100"])["new"].values()) == 0
+    em = R.gs_ref(GS["send_loss37_em"])["em"]
+    assert em[1::2].sum() > 0 and (em[0::2] + em[1::2]) .sum() == 2 * sum(
+        len(R.gs_ref(GS["send_loss37_em"])["WB"][ms // 8]) for t, v in R.gs_ref(GS["send_loss37_em"])["tin"].items()
+        for ms in v if t != GS["send_loss37_em"]["targets"] // 2)
+
+
+def test_gs_apply_case_holds_the_shapes_it_names():
+    c = GS["apply_gains"]
+    r = R.gs_ref(c)
+    assert [len(r["new"][t]) for t in range(7)] == c["gains"] == [0, 1, 8, 9, 64, 65, 4096 + 65]
+    reborn = int(((r["S"] & R.S16_REBORN) != 0).sum())
+    assert reborn == len(r["hist"]) > 0 and reborn < sum(c["gains"]) // 2, "stale entries of an earlier gossip are no rebirth"
+    assert r["rc_ndrop"].sum() > 0 and len(r["routed"]) > 0 and r["rc_ndrop"][5] == 0, "dead_rx routes every receipt of target 5"
+    assert r["fexp"] == [1, 2, 40, 41, 2240, 2241, 2244] and r["free"] == [2240, 2241, 2244] and 2 in R.gs_bits(c["DM"]) - r["DM"]
+    assert r["err"] == 0 and R.gs_ref(GS["apply_slife"])["err"] == R.E_SLIFE and R.gs_ref(GS["apply_rcap_short"])["err"] == R.E_RECEIPTS
+
+
+def test_gs_contact_cases_encode_their_explicit_answer():
+    """Every replayed gossip of a contact case is one its target never held (the S plane says so, and so does its ring), so
+    `t not in infectedFrom_m(g)` and the send happens; the events sit where the case says."""
+    c = GS["contacts"]
+    r = R.gs_ref(c)
+    k = c["k"]
+    for v in r["rp"] + r["slow"]:
+        g, ms = v >> 32, v & R.M32
+        t = int(c["T"][ms // c["F"]][ms % c["F"]])
+        assert c["S"][t][g] == 0 and g not in R.gs_bits(c["HB"][t])
+    assert [r["tcontact"][ms] for ms in (0, 17)] == [0, 1], "a contact at the cut and one tick after it"
+    assert r["cev"][64][0] == R.CEV and r["cev"][81][0] == R.CEV + 1 and r["cin"][81] == 0xFFFFFFFE
+    assert r["cin"][49] == R.NEVER and r["cev"][113][1] == k - 16 and len(r["rx"]) == 3
+    assert R.gs_ref(GS["contacts_cev1"])["cin"][64] == 0xFFFFFFFE
+    assert R.gs_ref(GS["contacts_crcap1"])["fb"][R.FB_RX_ALL] == 2 and R.gs_ref(GS["contacts_rpcap_short"])["err"] == R.E_CONTACTS
+    big = GS["contacts_logw128"]
+    assert any(t2 == k - 6 and e >= 64 for e, t2 in enumerate(big["log_tick"][15].tolist())), "the contact lies in the second pass"
+
+
+@pytest.mark.parametrize("name", list(R.gs_replay_cases()))
+def test_gs_replay_case_encoding_against_its_explicit_sets(name):
+    """The simulation's infectedFrom sets against what it wrote down for the engine: every holder's set is the members whose
+    logged rounds targeted it while both held the gossip (a lossless link: each such send arrived); a window gossip whose
+    target is in the set is among the sends the reference diverts to the replay lists, never on the fast path."""
+    c = GS[name]
+    r = R.gs_ref(c)
+    diverted = {(v >> 32, v & R.M32) for v in r["rp"] + r["slow"]}
+    for ms, t in ((m * c["F"] + s, int(c["T"][m][s])) for m in range(c["N"]) if c["tround"][m] for s in range(int(c["tcnt"][m]))):
+        m = ms // c["F"]
+        for g in r["WB"][m]:
+            if t in c["infected"][m, g]:
+                assert (g, ms) in diverted, (name, g, ms)
+    for (x, g), inf in c["infected"].items():
+        assert g in R.gs_bits(c["HB"][x]) and x not in inf
+        for y in inf:  # y's log holds a round that targeted x at or after x's receipt less the latency
+            cx = R.gs_s_get(c, int(c["S"][x][g]), g, c["k"] + c["lat"])
+            assert any(t2 != R.NEVER and t2 + c["lat"] >= cx and x in c["log_tg"][y][e][:c["log_cnt"][y][e]].tolist()
+                       for e, t2 in enumerate(c["log_tick"][y].tolist())), (name, x, g, y)
+    blocked = {(g, ms) for g, ms in diverted if int(c["T"][ms // c["F"]][ms % c["F"]]) in c["infected"][ms // c["F"], g]}
+    want = {"replay_a_c_e": ({(0, 0)}, {1, 2}), "replay_d_slow": ({(0, 0)}, {1, 2}), "replay_b_older": (set(), {0}),
+            "replay_f_rebirth": ({(0, 0)}, set())}[name]
+    assert (blocked, r["new"][1]) == want, (name, blocked, r["new"][1])
+    assert (len(r["slow"]) > 0) == (name == "replay_d_slow")
+    if name in ("replay_b_older", "replay_f_rebirth"):
+        assert c["S"][0][0] & R.S16_REBORN and len(R.gs_hist_decode(c["hist"])) >= 1, "m's current incarnation is a rebirth"
+    if name == "replay_a_c_e":
+        assert (2, 0) not in diverted, "(e) the gossip created after the contact arrived takes the fast path"
+
+
+def test_gs_pack_round_trip():
+    c = GS["contacts"]
+    params, inp, out = R.gs_pack(c)
+    got = R.gs_unpack(c, out)
+    assert len(params) == len(R.GS_PARAMS) == 27 and inp.nbytes % 8 == 0
+    for f in ("HB", "WB", "S", "rg", "rhead", "rtail", "slot_exp", "hist"):
+        assert np.array_equal(got[f], c[f]), f
+    assert got["free_top"] == c["free_top"] and got["rc_n"] == 0 and (got["tin"] == R.GS_SENT).all()
