@@ -323,7 +323,8 @@ static int alloc_table(swim_handle* h) {
   A(d.rowk, NV * d.NS) A(d.rowa, NV * d.NS) A(d.fdl, NV * d.LCAP) A(d.gl, NV * d.LCAP)
   Z(d.subs, NL * SUBCAP * 4) A(d.paths, NL * d.PCAP * 5) A(d.fetch, NL * d.FCAP * FREC) A(d.groups, NL * d.GRCAP * GREC)
   A(d.tround, N) Z(d.tcnt, N) A(d.tspread, N) A(d.tperiod, N) A(d.T, N * d.F) A(d.tcontact, N * d.F)
-  A(d.slow, d.SLOWCAP) A(d.slow_n, 1) A(d.rp, d.RPCAP) A(d.rp_n, 1) A(d.start_tick, N) A(d.jseed_n, N) A(d.jseeds, 16 * N)
+  // (slow_n, rp_n: the gossip plane resets them, but tick_flag publishes them for grow_caps from the first tick on)
+  A(d.slow, d.SLOWCAP) Z(d.slow_n, 1) A(d.rp, d.RPCAP) Z(d.rp_n, 1) A(d.start_tick, N) A(d.jseed_n, N) A(d.jseeds, 16 * N)
   A(d.md_uidx, N) A(d.mcfg, 4 * N) A(d.md_ver, NL * MDU) A(d.churn_q, 2ull * d.churn) Z(d.ucnt, N) A(d.cin, N * d.F)
   Z(d.HB, (uint64_t)d.QW * N) Z(d.WB, (uint64_t)d.QW * N) A(d.cev, N * d.F * CEVW)
   A(d.rg, (uint64_t)d.BCAP * N) A(d.rhead, N) A(d.rwin, N) A(d.rseen, N) A(d.rtail, N) A(d.rwl, N) A(d.nrwl, 1)
