@@ -1017,10 +1017,13 @@ int swimdbg_scalars(swim_handle* h, uint32_t m, uint64_t* out) {
   if (!h || !owns(h, m)) return SWIM_EINVAL;
   HIPCK(hipStreamSynchronize(h->stream));
   MS ms;
-  uint32_t ns = 0;
+  uint32_t ns = 0, ng = 0, fg = 0;
   HIPCK(hipMemcpy(&ms, h->d.ms + m, sizeof(MS), hipMemcpyDeviceToHost));
   HIPCK(hipMemcpy(&ns, h->d.nextSync + m, 4, hipMemcpyDeviceToHost));
-  const uint32_t v[6] = {ms.cidCnt, ms.syncSeq, ms.gCounter, ns, ms.fdPeriod, ms.gPeriod};
+  HIPCK(hipMemcpy(&ng, h->d.nextGossip + m, 4, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(&fg, h->d.firstGossip + m, 4, hipMemcpyDeviceToHost));
+  const uint32_t gp = fg == NEVER ? 0u : (ng - fg) / h->d.gossip_t;  // gossip_period (dev_util.h), on the host
+  const uint32_t v[6] = {ms.cidCnt, ms.syncSeq, ms.gCounter, ns, ms.fdPeriod, gp};
   for (int i = 0; i < 6; ++i) out[i] = (i == 3 && v[i] == NEVER) ? ~0ull : v[i];
   out[6] = ms.npath;
   out[7] = ms.nsub;

@@ -411,6 +411,13 @@ __device__ __forceinline__ uint32_t rounds_before(const Dev& d, uint32_t x, uint
   if (f == NEVER || c <= f) return 0;
   return div_gt(d, c - f + d.gossip_t - 1);
 }
+// A member's gossip period (GossipProtocolImpl's `period`: the doSpreadGossip rounds it has run) from its nextGossip
+// (ng) and firstGossip (fg). No word stores it: the two are set together (k_init_members, k_join), every round adds
+// gossip_t to nextGossip (the triage's empty round, p6_periodic), and a dead or dormant member runs none, so the
+// difference is an exact multiple of gossip_t. fg == NEVER (no round scheduled): 0.
+__device__ __forceinline__ uint32_t gossip_period(const Dev& d, uint32_t ng, uint32_t fg) {
+  return fg == NEVER ? 0u : div_gt(d, ng - fg);
+}
 
 // ClusterMath (ClusterMath.java:99-125): gossipPeriodsToSpread, gossipPeriodsToSweep (from the spread), and
 // suspicionTimeout in ticks; swim_selftest_eval exposes these exact functions for the known-answer tests

@@ -155,7 +155,8 @@ __host__ __device__ __forceinline__ uint64_t sync_entry_size(uint32_t MW) { retu
 // a member's body-only state (member_tick_body's ML fields): one 128-B line per member
 struct alignas(16) MS {
   uint32_t tsize, fdLen, gLen, fdPeriod;
-  uint32_t gPeriod, gCounter, cidCnt, syncSeq;
+  // rsv_period: reserved, always 0 (the gossip period once kept here is derived: gossip_period, dev_util.h)
+  uint32_t rsv_period, gCounter, cidCnt, syncSeq;
   uint32_t evSeq, initDeadline, initCidBase, initN;
   uint32_t nsub, npath, nfetch, fnext;  // fnext: earliest tick at which a pending metadata fetch needs the member
   int32_t pingIdx, remoteIdx;

@@ -26,7 +26,7 @@ __global__ void k_init_members(Dev d) {
   d.ms[m].tsize = pre ? d.N : 1;
   d.ms[m].fdLen = pre ? d.N - 1 : 0;
   d.ms[m].gLen = pre ? d.N - 1 : 0;
-  d.ms[m].fdPeriod = d.ms[m].gPeriod = d.ms[m].gCounter = 0;
+  d.ms[m].fdPeriod = d.ms[m].rsv_period = d.ms[m].gCounter = 0;
   d.nextPing[m] = pre ? 1 + init_draw(d, m, 1, 0) % d.ping_t : d.ping_t;
   uint32_t ng = pre ? 1 + init_draw(d, m, 2, 0) % d.gossip_t : d.gossip_t;
   d.nextGossip[m] = ng;
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(256) k_hash(Dev d, uint64_t* out, uint32_t now
     o6[4] = red[3][0];
     uint64_t ns = d.nextSync[m] == NEVER ? ~0ull : (uint64_t)d.nextSync[m];
     o6[5] = hpair(hpair(hpair(d.ms[m].cidCnt, d.ms[m].syncSeq), d.ms[m].gCounter), ns) +
-            mix64((uint64_t)d.ms[m].fdPeriod * 3 + (uint64_t)d.ms[m].gPeriod * 7);
+            mix64((uint64_t)d.ms[m].fdPeriod * 3 + (uint64_t)gossip_period(d, d.nextGossip[m], d.firstGossip[m]) * 7);
   }
 }
 

@@ -74,8 +74,9 @@ __device__ __forceinline__ bool member_triage(const Dev& d, uint32_t m, uint32_t
         d.tround[m] = 0;
         return false;
       }
-      if (held == 0) {  // doSpreadGossip with no gossips: period++ only (GossipProtocolImpl.java:141-146)
-        d.ms[m].gPeriod++;
+      // doSpreadGossip with no gossips: period++ only (GossipProtocolImpl.java:141-146); the period is derived from
+      // nextGossip (gossip_period), so the member's record is not touched
+      if (held == 0) {
         d.nextGossip[m] = ng + d.gossip_t;
         d.tround[m] = 0;
         return false;

@@ -501,8 +501,9 @@ __device__ __forceinline__ void do_ping(ML& L) {
 // the gossip data plane (gossip.hip) from T / tspread / tperiod; the round is logged for infectedFrom replay.
 __device__ __forceinline__ void do_spread_gossip(ML& L) {
   const Dev& d = *L.d;
-  uint32_t period = L.gPeriod++;
   if (L.held == 0) return;
+  // period = gPeriod++ (:140): the value before this round's advance (p6_periodic has added gossip_t to nextGossip)
+  const uint32_t period = gossip_period(d, L.nextGossip - d.gossip_t, d.firstGossip[L.m]);
   uint32_t F = d.F;
   uint32_t* T = d.T + (size_t)L.m * F;
   uint32_t cnt;

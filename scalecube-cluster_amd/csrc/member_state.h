@@ -16,7 +16,7 @@ enum : uint32_t { P_DIRECT = 0x10, P_REQ = 0x20, P_ARRIVE = 9 };
 struct ML {
   const Dev* d;
   uint32_t m, k, N;
-  uint32_t tsize, fdLen, gLen, fdPeriod, gPeriod, gCounter, nextPing, nextGossip, nextSync, cidCnt, syncSeq, evSeq,
+  uint32_t tsize, fdLen, gLen, fdPeriod, gCounter, nextPing, nextGossip, nextSync, cidCnt, syncSeq, evSeq,
       held, timerMin, initFlags, initDeadline, initCidBase, initN, nsub, npath, nfetch;
   int ep;          // NetworkEmulator settings epoch of tick k (epoch_at, looked up once)
   uint32_t fnext;  // earliest tick at which a pending fetch needs the member (hop, arrival or timeout); NEVER: none
@@ -297,7 +297,7 @@ __device__ __forceinline__ void ml_init(ML& L, const Dev& d, uint32_t m, uint32_
     const uint4* mp = (const uint4*)(d.ms + m);
     const uint4 w0 = mp[0], w1 = mp[1], w2 = mp[2], w3 = mp[3], w4 = mp[4];
     L.tsize = w0.x, L.fdLen = w0.y, L.gLen = w0.z, L.fdPeriod = w0.w;
-    L.gPeriod = w1.x, L.gCounter = w1.y, L.cidCnt = w1.z, L.syncSeq = w1.w;
+    L.gCounter = w1.y, L.cidCnt = w1.z, L.syncSeq = w1.w;  // (w1.x: MS::rsv_period)
     L.evSeq = w2.x, L.initDeadline = w2.y, L.initCidBase = w2.z, L.initN = w2.w;
     L.nsub = w3.x, L.npath = w3.y, L.nfetch = w3.z, L.fnext = w3.w;
     L.pingIdx = (int32_t)w4.x, L.remoteIdx = (int32_t)w4.y, L.evHash = ((uint64_t)w4.w << 32) | w4.z;
@@ -362,7 +362,7 @@ __device__ __forceinline__ void ml_store(ML& L) {
   {  // the body-only state: five 16-B stores into the member's record
     uint4* mp = (uint4*)(d.ms + m);
     mp[0] = make_uint4(L.tsize, L.fdLen, L.gLen, L.fdPeriod);
-    mp[1] = make_uint4(L.gPeriod, L.gCounter, L.cidCnt, L.syncSeq);
+    mp[1] = make_uint4(0u, L.gCounter, L.cidCnt, L.syncSeq);
     mp[2] = make_uint4(L.evSeq, L.initDeadline, L.initCidBase, L.initN);
     mp[3] = make_uint4(L.nsub, L.npath, L.nfetch, L.fnext);
     mp[4] = make_uint4((uint32_t)L.pingIdx, (uint32_t)L.remoteIdx, (uint32_t)L.evHash, (uint32_t)(L.evHash >> 32));
