@@ -326,6 +326,52 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
 int swim_debug_prim_eval(uint32_t op, const uint32_t* params, size_t n_params, const void* in, size_t in_bytes,
                          void* out, size_t out_bytes, uint32_t device);
 
+/* Injected gossip receipts: the receipts of the next tick's P4 (onMembershipGossip -> updateMembership,
+ * MembershipProtocolImpl.java:401-408,475-541) set by the caller on a live handle, so that a test chooses the batch
+ * sizes, subjects, orders and pre-states that the lane-serial fold (member.hip p4_receipts) and the wave version
+ * (inbox.hip k_inbox_apply) must agree on. One GPU, FULL mode, stored tables; a multi-device, row- or slot-sharded or RUMOR
+ * handle is SWIM_EINVAL. Host copies only: the kernels that run the receipts are the ones a step launches.
+ *
+ * swim_debug_receipts_set, between steps, installs for the handle's next tick k:
+ *   recs   [n_recs][6] words, one gossip each. SWIM_DEBUG_REC_MEMBER: subject, status (1 ALIVE, 2 SUSPECT, 3 DEAD),
+ *          incarnation, then the gossip id (origin member, counter). SWIM_DEBUG_REC_USER: origin, payload low word,
+ *          payload high word, 0, the gossip's counter (GossipProtocolImpl user gossips: the GOSSIP event's fields).
+ *   lists  groups of words: member, dropped receipts (Dev::rc_ndrop: receipts the routing found unable to change the
+ *          row, counted as record compares), count, then `count` indices into recs in the order P4 takes them. Each
+ *          member at most once; the same record may be listed for many members and several times for one.
+ *   split  1: the member launch of tick k is the split triple (k_member_tick BODY_SPLIT, k_inbox_apply, BODY_RESUME: the
+ *          launch that follows a gossip plane), 0: the single BODY_FULL launch.
+ * Each record takes one gossip slot off the top of the free stack (slot_subj, slot_key, slot_gid written, slot_used left
+ * 0: neither the gossip plane nor the state hash sees it; a gossip the tick creates cannot take the slot). The next
+ * step of one tick runs tick k on the one-tick path (no speculative or lister-free batch); everything after the member
+ * launch runs as on any tick. SWIM_EINVAL before anything is written: a subject, origin or member >= N; a status
+ * outside 1..3; an unknown record kind; an index >= n_recs; a member listed twice; more receipts in all than the routed-
+ * receipt capacity (swim_debug_caps SWIM_CAP_RECEIPTS); more records than free slots; a handle with a gossip slot in use,
+ * a routed receipt pending, queued user gossips or an injection not yet read back. An incarnation >= 2^30 is not
+ * refused: it reaches the kernels' own E_INC path (the step returns SWIM_ECAPACITY).
+ *
+ * swim_debug_receipts_read, after that step: out[n][SWIM_DEBUG_RD_WORDS + SWIM_DEBUG_FREC * fetch_cap] for members
+ * [first, first + n): tsize, cidCnt, nfetch, fnext, timerMin, held (the member's gossip count), gCounter, evSeq, the
+ * length of the member's write log of tick k (0 when it logged nothing in k; SWIM_DEBUG_TL + 1: overflowed), its
+ * SWIM_DEBUG_TL entries (0 past the length), then the first min(nfetch, fetch_cap) pending metadata fetches, 8 words each:
+ * correlation id, subject, incarnation, status | reason << 8 | added << 16 | stage << 24, group, deadline tick, next hop
+ * tick, metadata version (0 past nfetch). fetch_cap <= swim_config.pending_fetch_cap (256 when that is 0).
+ * msg_out (may be null): [2 + 3 N] = arena rows taken in tick k's message buffer, its messages, then per sender the
+ * messages of that buffer whose payload is an arena row (a snapshot of the row as it was sent), then every member's
+ * routed-receipt count and fill as the tick left them (Dev::rc_cnt, rc_fill: 0 once P4 or the triage took the list).
+ * The first read after a set also puts the injected slots back on top of the free stack, so stepping goes on as on any
+ * handle; n = 0 with msg_out null does only that. SWIM_EINVAL: no injection since create, a range past N, fetch_cap
+ * past the handle's. */
+#define SWIM_DEBUG_REC_MEMBER 0u
+#define SWIM_DEBUG_REC_USER 1u
+#define SWIM_DEBUG_TL 16u
+#define SWIM_DEBUG_FREC 8u
+#define SWIM_DEBUG_RD_WORDS 25u
+int swim_debug_receipts_set(swim_handle* h, const uint32_t* recs, size_t n_recs, const uint32_t* lists, size_t n_words,
+                            uint32_t split);
+int swim_debug_receipts_read(swim_handle* h, uint32_t first, uint32_t n, uint32_t fetch_cap, uint32_t* out,
+                             uint32_t* msg_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 //   diag.hip      SWIM_STATS / SWIM_EXP dumps, profile events
 //   group.hip     swim_config.n_gpus > 1: one handle over several shard handles
 //   api.hip       the other extern "C" entry points: fault injection, readback
+//   debug_receipts.hip  swim_debug_receipts_set / _read: injected P4 receipts (tests)
 // The device side (engine.h, spec.h, dev_util.h): member.hip (member control: triage, phases, k_member_tick_t) over
 // member_state.h (a member's state, row writes, SYNC sends) and member_proto.h (the protocol handlers), inbox.hip
 // (k_inbox_apply: P4 of a parked member on one wave), user_gossip.hip (host-queued gossips, churn), sync_diff.hip (SYNC
@@ -101,6 +102,11 @@ struct swim_handle {
   // timing aid (SWIM_STATS): the gossip plane's work per tick on stderr (routed receipts, targets, active groups,
   // replay / slow-path sends, contact pairs, RX rows); one stream wait per tick
   bool stats = getenv("SWIM_STATS") != nullptr;
+  // swim_debug_receipts_set (debug_receipts.hip): the gossip slots its records took off the free stack, the tick they
+  // were installed for, and whether an injection is there to read back
+  std::vector<uint32_t> dbg_slots;
+  uint64_t dbg_tick = 0;
+  bool dbg_armed = false;
   Group* grp = nullptr;  // n_gpus > 1: every call is forwarded to the shards (d holds shard 0's constants only)
 };
 

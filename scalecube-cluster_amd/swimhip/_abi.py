@@ -249,7 +249,42 @@ DEBUG_SIGNATURES = {
     "swim_debug_dirty_check": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
     "swim_debug_prim_eval": (C.c_int, [C.c_uint32, _U32P, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_uint32]),
+    "swim_debug_receipts_set": (C.c_int, [_H, _U32P, C.c_size_t, _U32P, C.c_size_t, C.c_uint32]),
+    "swim_debug_receipts_read": (C.c_int, [_H, C.c_uint32, C.c_uint32, C.c_uint32, _U32P, _U32P]),
 }
+# swim_debug_receipts_set / _read (include/swimhip_debug.h): record kinds, write-log entries, words per fetch record,
+# fixed words per member of the read-back
+DEBUG_REC_MEMBER, DEBUG_REC_USER, DEBUG_TL, DEBUG_FREC, DEBUG_RD_WORDS = 0, 1, 16, 8, 25
+RD_NAMES = ["tsize", "cidCnt", "nfetch", "fnext", "timerMin", "held", "gCounter", "evSeq", "tl_n"]
+
+
+def debug_receipts_set(lib, handle, recs, lists, split):
+    """Install the next tick's routed receipts (include/swimhip_debug.h swim_debug_receipts_set); the return code.
+    recs: 6-word tuples; lists: {member: (ndrop, [record indices])} or a flat word list."""
+    fn = lib.swim_debug_receipts_set
+    fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_receipts_set"]
+    flat = [int(x) & 0xFFFFFFFF for r in recs for x in r]
+    assert len(flat) == 6 * len(recs)
+    if isinstance(lists, dict):
+        words = []
+        for m, (nd, idx) in lists.items():
+            words += [m, nd, len(idx), *idx]
+    else:
+        words = list(lists)
+    a = (C.c_uint32 * max(1, len(flat)))(*flat)
+    b = (C.c_uint32 * max(1, len(words)))(*[int(x) & 0xFFFFFFFF for x in words])
+    return fn(handle, a, len(recs), b, len(words), 1 if split else 0)
+
+
+def debug_receipts_read(lib, handle, first, n, n_members, fetch_cap=0, messages=False):
+    """(rc, out[n][DEBUG_RD_WORDS + DEBUG_FREC * fetch_cap], msg[2 + 3 * n_members] or None) after the injected tick."""
+    import numpy as np
+    fn = lib.swim_debug_receipts_read
+    fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_receipts_read"]
+    out = np.zeros((max(n, 1), DEBUG_RD_WORDS + DEBUG_FREC * fetch_cap), dtype=np.uint32)
+    msg = np.zeros(2 + 3 * n_members, dtype=np.uint32) if messages else None
+    rc = fn(handle, first, n, fetch_cap, out.ctypes.data_as(_U32P), msg.ctypes.data_as(_U32P) if messages else None)
+    return rc, out[:n], msg
 # swim_debug_prim_eval: ops, and the sub-ops of PRIM_WAVE and PRIM_ARITH (include/swimhip_debug.h has the layouts)
 (PRIM_SCAN, PRIM_SEG_SORT, PRIM_ROUTING, PRIM_WAVE, PRIM_DIRTY, PRIM_ARITH, PRIM_FEISTEL, PRIM_RING_MOVE,
  PRIM_SYNC_DIFF, PRIM_XPACK, PRIM_PACK_B, PRIM_INLINE_IN, PRIM_XUNPACK, PRIM_GOSSIP) = range(14)

@@ -2424,3 +2424,351 @@ def gs_cases():
     cs["apply_rcap_short"] = gs_apply_case(RCAP=len(gs_ref(cs["apply_gains"])["routed"]) - 1)
     cs["apply_slife"] = gs_apply_case(slife=True)
     return cs
+
+
+# ------------------------------------------------------------------- P4: the gossip first-receipt phase of one member
+# onMembershipGossip -> updateMembership(r1, MEMBERSHIP_GOSSIP) (MembershipProtocolImpl.java:401-408,475-541; SEMANTICS.md
+# §7) for one member and one ordered receipt list, as a serial fold over dictionaries: the yardstick of
+# tests/test_gpu_p4.py for both device versions of the phase (the lane-serial fold and the wave version). Loss 0, no
+# link delay, no per-member config, every metadata version 0.
+P4_ABSENT, P4_ALIVE, P4_SUSPECT, P4_DEAD = 0, 1, 2, 3
+P4_INC_LIMIT = 1 << 30  # an incarnation the key plane cannot hold: the engine's E_INC
+P4_TL = 16  # entries of a member's per-tick write log; its length saturates at P4_TL + 1
+P4_COUNTS = [0, 1, 7, 8, 9, 63, 64, 65, 128, 129, 200]
+P4_SLOW_AT = [0, 31, 63, 64, 69]  # positions of the slow receipt in a list of 70 (69: last)
+P4_SLOW_KINDS = ["own_alive", "own_suspect", "dead", "absent", "user"]
+P4_ACCEPTED = [16, 17, 40]
+
+
+def p4_is_overrides(s1, i1, s0, i0):
+    """MembershipRecord.isOverrides (MembershipRecord.java:66-84); s0 = P4_ABSENT is `r0 == null`."""
+    if s0 == P4_ABSENT:
+        return s1 == P4_ALIVE
+    if s0 == P4_DEAD:
+        return False
+    if s1 == P4_DEAD:
+        return True
+    if i1 == i0:
+        return s1 != s0 and s1 == P4_SUSPECT
+    return i1 > i0
+
+
+def p4_ceil_log2(n):
+    """ClusterMath.ceilLog2 (ClusterMath.java:133-135): the bit length."""
+    return int(n).bit_length()
+
+
+def p4_member(m, N, fd, gl):
+    """Member m of a PRECONVERGED cluster before its first tick: every subject ALIVE at incarnation 0 with known
+    metadata, no timer, no fetch. fd / gl: its pingMembers and remoteMembers lists as the engine shuffled them."""
+    return {"m": m, "row": {s: [P4_ALIVE, 0, True, 0] for s in range(N)}, "tsize": N, "cid": 0, "fetch": [],
+            "fnext": NEVER, "timerMin": NEVER, "gcnt": 0, "evseq": 0, "fd": list(fd), "gl": list(gl)}
+
+
+def p4_fold(st, k, ndrop, receipts, dead, cfg):
+    """One tick's P4 of member state `st` (changed in place) at tick k. receipts: ("M", subject, status, incarnation) or
+    ("U", origin, payload, counter) in order; ndrop: receipts the routing dropped (compares only); dead: the members
+    that are dead at k; cfg: suspicion_mult, ping_t, md_t, lat (ticks). Returns the tick's events, write log, its
+    length, counter deltas, gossips created (subject, status, incarnation) and whether an incarnation >= 2^30 was
+    written."""
+    m = st["m"]
+    out = {"events": [], "tl": [], "tl_n": 0, "R": 0, "W": 0, "M": 0, "E": 0, "LOST": 0, "gossips": [], "einc": False}
+    if m in dead:  # a crashed member holds no P4: its receipts are dropped
+        return out
+    out["R"] += ndrop
+    last = [None]
+
+    def wrote(s):  # the tick's write log: a repeat of the last subject is one entry; the length saturates
+        if out["tl_n"] and last[0] == s:
+            return
+        if out["tl_n"] < P4_TL:
+            out["tl"].append(s)
+        if out["tl_n"] <= P4_TL:
+            out["tl_n"] += 1
+        last[0] = s
+
+    def event(typ, subj, old, new, pad=0):
+        out["events"].append((k, m, st["evseq"], typ, subj, old, new, pad))
+        st["evseq"] += 1
+        out["E"] += 1
+
+    def fetch(subj, s1, i1, added):
+        cid = st["cid"]
+        st["cid"] += 1
+        out["M"] += 1
+        if subj in dead:  # connection refused: the request is lost, nothing is recorded
+            out["LOST"] += 1
+            return
+        st["fetch"].append([cid, subj, i1, s1 | (1 << 8) | (added << 16) | (1 << 24), M32, k + cfg["md_t"],
+                            k + cfg["lat"], M32])
+        st["fnext"] = min(st["fnext"], k + cfg["md_t"], k + cfg["lat"])
+
+    for r in receipts:
+        if r[0] == "U":  # listenGossips: not membership, no record compare
+            event("GOSSIP", r[1], r[2] & M32, (r[2] >> 32) & M32, r[3])
+            continue
+        _, subj, s1, i1 = r
+        out["R"] += 1
+        row = st["row"].get(subj)
+        s0, i0 = (row[0], row[1]) if row else (P4_ABSENT, 0)
+        if not p4_is_overrides(s1, i1, s0, i0):
+            continue
+        if subj == m:  # refute: max(inc) + 1, the status kept, one gossip, no event
+            row[1] = max(i0, i1) + 1
+            out["einc"] |= row[1] >= P4_INC_LIMIT
+            out["W"] += 1
+            wrote(subj)
+            st["gcnt"] += 1
+            out["gossips"].append((subj, s0, row[1]))
+            continue
+        out["einc"] |= i1 >= P4_INC_LIMIT
+        out["W"] += 1
+        wrote(subj)
+        if s1 == P4_DEAD:  # the row goes, with its metadata and its timer
+            del st["row"][subj]
+            st["tsize"] -= 1
+            event("REMOVED", subj, 0 if row[2] else None, None)
+            for name in ("fd", "gl"):
+                if subj in st[name]:
+                    st[name].remove(subj)
+            continue
+        if row is None:
+            row = st["row"][subj] = [s1, i1, False, 0]
+            st["tsize"] += 1
+        row[0], row[1] = s1, i1
+        if s1 == P4_SUSPECT:
+            if row[3] == 0:  # computeIfAbsent
+                row[3] = k + cfg["suspicion_mult"] * p4_ceil_log2(st["tsize"]) * cfg["ping_t"]
+                st["timerMin"] = min(st["timerMin"], row[3])
+        else:
+            row[3] = 0  # cancel
+        if s0 == P4_ABSENT:
+            fetch(subj, s1, i1, 1)
+        elif i0 < i1:
+            fetch(subj, s1, i1, 0)
+    return out
+
+
+def p4_hops(st, k, dead, cfg):
+    """What the tick does to the member's pending fetches before P4 (swim_create takes a latency of one tick only, so
+    the requests of tick k - 1 reach their subjects at k): a live subject answers with GET_METADATA_RESP carrying its
+    metadata version 0, one message, and the record waits for the arrival at k + lat; a dead one answers nothing and
+    only the timeout remains. Returns the messages sent."""
+    sent = 0
+    if st["m"] in dead:
+        return 0
+    for f in st["fetch"]:
+        if f[3] >> 24 == 1 and f[6] == k:
+            if f[1] in dead:
+                f[3] &= 0x00FFFFFF
+            else:
+                sent += 1
+                f[3] = (f[3] & 0x00FFFFFF) | (2 << 24)
+                f[6], f[7] = k + cfg["lat"], 0
+    due = [min(f[5], f[6]) if f[3] >> 24 else f[5] for f in st["fetch"]]
+    if any(f[5] <= k or (f[3] >> 24 == 2 and f[6] <= k) for f in st["fetch"]):
+        raise ValueError("an arrival or a timeout in this tick: outside what this reference restates")
+    st["fnext"] = min(due) if due else st["fnext"]
+    return sent
+
+
+def p4_row_words(st, N):
+    """The member's table as swim_read_row returns it: inc | status << 32 | metadata known << 34 | deadline << 35."""
+    out = np.zeros(N, np.uint64)
+    for s, (s0, i0, meta, timer) in st["row"].items():
+        out[s] = (i0 & M32) | (s0 << 32) | (int(meta) << 34) | (timer << 35)
+    return out
+
+
+def p4_batch_accepts(key0, receipts):
+    """The batching claim of the wave version, restated on its own: on present rows, with no DEAD and no own-record
+    receipt, a receipt (subject, status, incarnation) is accepted iff its key inc << 2 | status is above the running
+    maximum of the row's key and the earlier keys of the same subject. key0: subject -> the row's key before the list.
+    Returns one bool per receipt."""
+    top = dict(key0)
+    acc = []
+    for s, s1, i1 in receipts:
+        key = (i1 << 2) | s1
+        acc.append(key > top[s])
+        top[s] = max(top[s], key)
+    return acc
+
+
+def p4_serial_accepts(key0, receipts):
+    """The same list through isOverrides one receipt after another (what p4_fold does)."""
+    row = {s: [k & 3, k >> 2] for s, k in key0.items()}
+    acc = []
+    for s, s1, i1 in receipts:
+        ok = p4_is_overrides(s1, i1, row[s][0], row[s][1])
+        acc.append(ok)
+        if ok:
+            row[s] = [s1, i1]
+    return acc
+
+
+def p4_pool(N, m, killed):
+    """The subjects member m's lists are about, in the order the patterns index them: every live other member,
+    starting after m."""
+    p = [s for s in range(N) if s != m and s not in killed]
+    r = m % len(p)
+    return p[r:] + p[:r]
+
+
+def p4_prep(p, top=P4_INC_LIMIT - 2):
+    """The preparation tick's receipts for a member with pool p (no own record, so no gossip is created): the pre-states
+    the tick under test meets. p[0], p[1] SUSPECT 0 (a timer held), p[2] ALIVE 2, p[3] SUSPECT 1, p[4], p[5] removed,
+    p[6] ALIVE 62, p[7] ALIVE 63 (the 8-bit key shadow's edge), p[8] SUSPECT top, p[9] ALIVE top (2^30 - 2: the
+    largest incarnation that can still rise)."""
+    return [("M", p[0], P4_SUSPECT, 0), ("M", p[1], P4_SUSPECT, 0), ("M", p[2], P4_ALIVE, 2), ("M", p[3], P4_SUSPECT, 1),
+            ("M", p[4], P4_DEAD, 0), ("M", p[5], P4_DEAD, 7), ("M", p[6], P4_ALIVE, 62), ("M", p[7], P4_ALIVE, 63),
+            ("M", p[8], P4_SUSPECT, top), ("M", p[9], P4_ALIVE, top)]
+
+
+def p4_fast(rng, p, n):
+    """n receipts that are fast after p4_prep unless an earlier one of the list removed their row: ALIVE / SUSPECT about
+    twelve present subjects at incarnations around the rows', so that one subject recurs within a batch, keys repeat
+    and stale records sit between accepted ones."""
+    subj = [p[0], p[1], p[2], p[3], p[6], p[7]] + p[10:16]
+    base = [0, 0, 2, 1, 62, 63] + [0] * 6
+    out = []
+    for _ in range(n):
+        j = int(rng.integers(0, len(subj)))
+        out.append(("M", subj[j], int(rng.integers(1, 3)), base[j] + int(rng.integers(0, 4))))
+    return out
+
+
+def p4_slow(kind, m, p, j=0):
+    """One receipt that the wave version hands to lane 0."""
+    return {"own_alive": ("M", m, P4_ALIVE, 1 + j), "own_suspect": ("M", m, P4_SUSPECT, 0),
+            "dead": ("M", p[11 + j], P4_DEAD, 0), "absent": ("M", p[4 + (j & 1)], P4_ALIVE, 5 + j),
+            "user": ("U", p[20], 0x1122334455667788 + j, 9 + j)}[kind]
+
+
+def p4_patterns(N, m, killed, name, top=P4_INC_LIMIT - 2):
+    """The receipt list of the tick under test for pattern `name` at member m."""
+    p = p4_pool(N, m, killed)
+    rng = np.random.default_rng(7000 + 131 * m + N)
+    A, S, D = P4_ALIVE, P4_SUSPECT, P4_DEAD
+    kind, _, arg = name.partition(":")
+    if kind == "count":
+        return p4_fast(rng, p, int(arg))
+    if kind == "triple":  # SUSPECT i / ALIVE i + 1 / SUSPECT i + 1 after `off` stale fast receipts
+        who, off = arg.split(",")
+        pad = [("M", p[12], A, 0)] * int(off)
+        if who == "notimer":
+            return pad + [("M", p[10], S, 0), ("M", p[10], A, 1), ("M", p[10], S, 1)]
+        if who == "timer":
+            return pad + [("M", p[0], S, 1), ("M", p[0], A, 2), ("M", p[0], S, 2)]
+        return pad + [("M", p[10], S, 0), ("M", p[0], S, 1), ("M", p[10], A, 1), ("M", p[0], A, 2), ("M", p[0], S, 2),
+                      ("M", p[10], S, 1)]
+    if kind == "stale":  # stale records between accepted ones, equal keys
+        return [("M", p[10], S, 1), ("M", p[10], A, 0), ("M", p[10], A, 1), ("M", p[10], S, 1), ("M", p[11], A, 0),
+                ("M", p[10], A, 2), ("M", p[10], A, 2), ("M", p[0], S, 0), ("M", p[0], A, 0), ("M", p[1], A, 1),
+                ("M", p[1], A, 1), ("M", p[1], S, 1), ("M", p[1], S, 1)]
+    if kind == "slow":
+        what, at = arg.split(",")
+        lst = p4_fast(rng, p, 69)
+        lst.insert(int(at), p4_slow(what, m, p))
+        return lst
+    if kind == "slow2":  # two slow receipts back to back, inside a batch and across its end
+        lst = p4_fast(rng, p, 100)
+        for at, (a, b) in ((63, ("own_alive", "absent")), (10, ("dead", "user"))):
+            lst[at:at] = [p4_slow(a, m, p, 1), p4_slow(b, m, p, 1)]
+        return lst
+    if kind == "allslow":
+        return [p4_slow(x, m, p, j) for j in range(3) for x in P4_SLOW_KINDS]
+    if kind == "accepted":  # distinct accepted subjects: the write log fills and overflows
+        n, fetching = arg.split(",")
+        return [("M", p[10 + j], A, 1) if fetching == "f" else ("M", p[10 + j], S, 0) for j in range(int(n))]
+    if kind == "incs":
+        top += 1
+        return [("M", p[6], S, 62), ("M", p[6], A, 63), ("M", p[7], A, 63), ("M", p[7], S, 63), ("M", p[7], A, 64),
+                ("M", p[6], S, 64), ("M", p[6], D, 3), ("M", p[8], A, top), ("M", p[9], S, top), ("M", p[9], A, top),
+                ("M", p[8], S, top - 1), ("M", p[8], S, top)]
+    if kind == "killed":  # subjects that are dead at the tick: the metadata request is lost
+        return [("M", killed[0], A, 1), ("M", p[10], A, 1), ("M", killed[1], S, 1), ("M", killed[1], A, 2),
+                ("M", killed[0], D, 0), ("M", killed[0], A, 4)]
+    if kind == "mixed":
+        lst = p4_fast(rng, p, int(arg))
+        for j in range(int(arg) // 9):
+            at = int(rng.integers(0, len(lst) + 1))
+            lst.insert(at, p4_slow(P4_SLOW_KINDS[int(rng.integers(0, 5))], m, p, j % 3))
+        return lst
+    if kind == "none":
+        return []
+    raise KeyError(name)
+
+
+def p4_pattern_names():
+    names = [f"count:{n}" for n in P4_COUNTS]
+    names += [f"triple:{w},{o}" for w in ("notimer", "timer", "both") for o in (0, 62)] + ["stale:"]
+    names += [f"slow:{w},{a}" for w in P4_SLOW_KINDS for a in P4_SLOW_AT] + ["slow2:", "allslow:"]
+    names += [f"accepted:{n},{f}" for n in P4_ACCEPTED for f in ("s", "f")] + ["incs:", "killed:"]
+    names += [f"mixed:{n}" for n in (30, 100, 150)] + ["none:"]
+    return names
+
+
+def p4_case(N, top=P4_INC_LIMIT - 2):
+    """The known-answer case at N members (top: the incarnation of the rows at the field's edge; a run that goes on for
+    many ticks takes a smaller one, since a member that hears of its own record at 2^30 - 1 refutes it with 2^30): kills (before the first tick), then per tick {member: (ndrop, receipts)} for
+    the preparation tick 0 and the tick under test 1. Every pattern runs at a member of its own, spread over the member
+    range (two blocks of k_member_tick at N = 300); the last two members are killed: one keeps receipts and dropped
+    receipts (nothing applied, counts cleared), one only dropped receipts; an idle live member has dropped receipts too."""
+    killed = [N - 1, N - 2]
+    names = p4_pattern_names()
+    stride = (N - 3) // len(names)
+    assert stride >= 1
+    prep, test, who = {}, {}, {}
+    for i, name in enumerate(names):
+        m = i * stride
+        who[m] = name
+        prep[m] = (0, p4_prep(p4_pool(N, m, killed), top))
+        test[m] = (5 if name in ("count:65", "slow:dead,31") else 0, p4_patterns(N, m, killed, name, top))
+    test[N - 3] = (3, [])  # idle, alive
+    who[N - 3] = "idle ndrop"
+    test[N - 2] = (4, [])  # dead, idle
+    test[N - 1] = (2, p4_fast(np.random.default_rng(5), p4_pool(N, 0, killed), 70))  # dead, with receipts
+    prep[N - 1] = (1, [("M", 0, P4_SUSPECT, 0)])
+    return {"N": N, "killed": killed, "ticks": [prep, test], "who": who}
+
+
+def p4_case_einc(N):
+    """One record at incarnation 2^30 in a serial-sized list and behind a batch boundary: every path reports E_INC."""
+    p0, p1 = p4_pool(N, 3, []), p4_pool(N, 40, [])
+    rng = np.random.default_rng(11)
+    a = [("M", p0[10], P4_ALIVE, 1), ("M", p0[10], P4_ALIVE, P4_INC_LIMIT), ("M", p0[12], P4_SUSPECT, 0)]
+    b = [("M", p1[10 + int(rng.integers(0, 6))], int(rng.integers(1, 3)), int(rng.integers(0, 4))) for _ in range(70)]
+    b.insert(64, ("M", p1[11], P4_SUSPECT, P4_INC_LIMIT))
+    return {"N": N, "killed": [], "ticks": [{3: (0, a), 40: (0, b)}], "who": {3: "einc short", 40: "einc at 64"}}
+
+
+def p4_pack(tick):
+    """{member: (ndrop, receipts)} as swim_debug_receipts_set takes it: the table of distinct records (6 words each) and
+    {member: (ndrop, indices)}."""
+    table, recs, lists = {}, [], {}
+    for m, (nd, lst) in tick.items():
+        idx = []
+        for r in lst:
+            if r not in table:
+                table[r] = len(recs)
+                if r[0] == "M":
+                    recs.append((0, r[1], r[2], r[3], r[1], len(recs)))
+                else:
+                    recs.append((1, r[1], r[2] & M32, (r[2] >> 32) & M32, 0, r[3]))
+            idx.append(table[r])
+        lists[m] = (nd, idx)
+    return recs, lists
+
+
+def p4_injectable(N, recs, lists, rcap, free_slots):
+    """swim_debug_receipts_set's own preconditions (include/swimhip_debug.h), restated for the CPU check."""
+    for r in recs:
+        if r[0] == 0 and not (r[1] < N and 1 <= r[2] <= 3 and r[4] < N):
+            return False
+        if r[0] == 1 and not (r[1] < N and r[4] == 0):
+            return False
+        if r[0] > 1:
+            return False
+    if any(m >= N or any(i >= len(recs) for i in idx) for m, (_, idx) in lists.items()):
+        return False
+    return sum(len(idx) for _, idx in lists.values()) <= rcap and len(recs) <= free_slots

@@ -6,7 +6,12 @@ updateMembership, MembershipProtocolImpl.java:401-408,475-541: a segmented prefi
 which receipts override, prefix sums place the metadata fetches and write-log entries in gossip-id order), and a second
 k_member_tick launch runs the parked members' P5 and P6. SWIM_CAPS hv=N lowers the threshold, so that every member with
 a receipt takes this path; the gossip-heavy scenarios must still reproduce the oracle's records bit for bit: the same
-tables, fetch lists, correlation ids, write logs, events and counters as the lane-serial P4."""
+tables, fetch lists, correlation ids, write logs, events and counters as the lane-serial P4.
+
+These runs meet whatever receipt mix their scenarios produce. The targeted cases (batches of exactly 64, 65 and 129
+receipts, one subject three times in a batch, slow receipts at chosen lanes, a full write log, incarnations at the edges
+of the key shadow and of the key field, snapshots of parked SYNC_ACK senders, more than 8192 parked members) are in
+tests/test_gpu_p4.py, on receipts installed by swim_debug_receipts_set."""
 import json
 from pathlib import Path
 

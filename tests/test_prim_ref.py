@@ -902,3 +902,112 @@ def test_gs_pack_round_trip():
     for f in ("HB", "WB", "S", "rg", "rhead", "rtail", "slot_exp", "hist"):
         assert np.array_equal(got[f], c[f]), f
     assert got["free_top"] == c["free_top"] and got["rc_n"] == 0 and (got["tin"] == R.GS_SENT).all()
+
+
+# ---------------------------------------------------------------------------------------------- P4 (tests/test_gpu_p4.py)
+P4_INCS = [0, 1, 2, 62, 63, 64, 2**30 - 2, 2**30 - 1]
+
+
+def test_p4_is_overrides_matches_the_oracle(oracle):
+    for s1 in range(1, 4):
+        for s0 in range(4):
+            for i1 in P4_INCS:
+                for i0 in P4_INCS:
+                    assert R.p4_is_overrides(s1, i1, s0, i0) == bool(oracle.swim_is_overrides(s1, i1, s0, i0)), \
+                        (s1, i1, s0, i0)
+    for n in (0, 1, 2, 3, 4, 94, 96, 127, 128, 300, 8320, 100_000):
+        assert R.p4_ceil_log2(n) == oracle.swim_ceil_log2(n), n
+
+
+def test_p4_batching_claim_equals_the_serial_fold():
+    """A few thousand seeded lists of fast receipts: present rows, ALIVE / SUSPECT records about other members."""
+    rng = np.random.default_rng(4242)
+    accepted = 0
+    for t in range(4000):
+        nsub = int(rng.integers(1, 6))
+        incs = [0, 1, 2, 3] if t % 3 else [61, 62, 63, 64]
+        key0 = {s: (int(rng.choice(incs)) << 2) | int(rng.integers(1, 3)) for s in range(nsub)}
+        lst = [(int(rng.integers(0, nsub)), int(rng.integers(1, 3)), int(rng.choice(incs)))
+               for _ in range(int(rng.integers(1, 140)))]
+        a, b = R.p4_batch_accepts(key0, lst), R.p4_serial_accepts(key0, lst)
+        assert a == b, (key0, lst)
+        accepted += sum(a)
+    assert accepted > 4000
+    # and through the whole fold: the rows it leaves are the largest key of each subject
+    st = R.p4_member(0, 8, range(1, 8), range(1, 8))
+    lst = [("M", int(rng.integers(1, 8)), int(rng.integers(1, 3)), int(rng.integers(0, 5))) for _ in range(300)]
+    R.p4_fold(st, 1, 0, lst, set(), {"suspicion_mult": 5, "ping_t": 10, "md_t": 30, "lat": 2})
+    for s in range(1, 8):
+        top = max([(0 << 2) | 1] + [(i << 2) | x for _, q, x, i in lst if q == s])
+        assert (st["row"][s][1] << 2) | st["row"][s][0] == top
+
+
+def test_p4_fold_known_answers():
+    cfg = {"suspicion_mult": 5, "ping_t": 10, "md_t": 30, "lat": 2}
+    st = R.p4_member(2, 8, [0, 1, 3, 4, 5, 6, 7], [7, 6, 5, 4, 3, 1, 0])
+    A, S, D = R.P4_ALIVE, R.P4_SUSPECT, R.P4_DEAD
+    r = R.p4_fold(st, 5, 2, [("M", 3, S, 0), ("M", 3, A, 1), ("M", 3, S, 1), ("M", 4, D, 0), ("M", 4, S, 3), ("M", 4, A, 2),
+                             ("M", 2, S, 0), ("U", 6, (9 << 32) | 8, 4), ("M", 7, A, 1), ("M", 5, A, 0)], {7}, cfg)
+    dl = 5 + 5 * 4 * 10  # bitlen(8) = 4
+    assert st["row"][3] == [S, 1, True, dl] and st["row"][4] == [A, 2, False, 0] and st["row"][2] == [A, 1, True, 0]
+    assert st["tsize"] == 8 and st["cid"] == 3 and st["timerMin"] == dl and st["fnext"] == 7 and st["gcnt"] == 1
+    # (SUSPECT 1 after ALIVE 1 is accepted without a fetch: the incarnation did not rise; the request to dead 7 is lost)
+    assert [f[:4] for f in st["fetch"]] == [[0, 3, 1, A | 1 << 8 | 1 << 24], [1, 4, 2, A | 1 << 8 | 1 << 16 | 1 << 24]]
+    assert st["fetch"][0][4:] == [R.M32, 35, 7, R.M32]
+    assert r["events"] == [(5, 2, 0, "REMOVED", 4, 0, None, 0), (5, 2, 1, "GOSSIP", 6, 8, 9, 4)]
+    assert st["fd"] == [0, 1, 3, 5, 6, 7] and st["gl"] == [7, 6, 5, 3, 1, 0]
+    assert (r["R"], r["W"], r["M"], r["E"], r["LOST"]) == (11, 7, 3, 2, 1) and r["gossips"] == [(2, A, 1)]
+    assert r["tl"] == [3, 4, 2, 7] and r["tl_n"] == 4 and not r["einc"]
+    r = R.p4_fold(st, 6, 0, [("M", s % 8, S, 9 + s // 8) for s in range(40) if s % 8 != 2], set(), cfg)
+    assert r["tl_n"] == R.P4_TL + 1 and len(r["tl"]) == R.P4_TL
+    dead = R.p4_fold(R.p4_member(1, 4, [], []), 0, 3, [("M", 0, S, 0)], {1}, cfg)
+    assert dead["R"] == 0 and dead["W"] == 0
+
+
+@pytest.mark.parametrize("N", [66, 96, 300])
+def test_p4_cases_meet_the_injector_preconditions(N):
+    c = R.p4_case(N)
+    names = set(c["who"].values())
+    assert {f"count:{n}" for n in R.P4_COUNTS} <= names and len(c["who"]) == len(names)
+    assert {f"slow:{w},{a}" for w in R.P4_SLOW_KINDS for a in R.P4_SLOW_AT} <= names
+    assert max(c["who"]) >= 256 or N < 256, "members of the second k_member_tick block take part"
+    slots = max(1024, 64 * N)  # swim_create's default slot table
+    for i, tick in enumerate(c["ticks"] + R.p4_case_einc(N)["ticks"]):
+        recs, lists = R.p4_pack(tick)
+        assert R.p4_injectable(N, recs, lists, 1 << 16, slots), i
+        assert len(set(recs)) == len(recs)
+    for m, (_, lst) in c["ticks"][0].items():  # the preparation tick creates no gossip: no own record
+        assert all(r[0] == "M" and r[1] != m for r in lst)
+    # the patterns are what they say, on the reference itself
+    cfg = {"suspicion_mult": 5, "ping_t": 10, "md_t": 30, "lat": 1}
+    by = {v: k for k, v in c["who"].items()}
+    res = {}
+    for name, m in by.items():
+        st = R.p4_member(m, N, [], [])
+        for k, tick in enumerate(c["ticks"]):
+            nd, lst = tick.get(m, (0, []))
+            assert R.p4_hops(st, k, set(c["killed"]), cfg) == (6 if k == 1 and m in c["ticks"][0] else 0)  # the six requests
+            # of the preparation tick
+            res[name] = (st, R.p4_fold(st, k, nd, lst, set(c["killed"]), cfg), lst)
+    for n in R.P4_COUNTS:
+        assert len(res[f"count:{n}"][2]) == n
+    for n in R.P4_ACCEPTED:  # n distinct accepted subjects: the write log overflows past 16
+        for f in "sf":
+            r = res[f"accepted:{n},{f}"][1]
+            assert r["W"] == n and r["tl_n"] == min(n, R.P4_TL + 1) and r["M"] == (n if f == "f" else 0)
+    for w in R.P4_SLOW_KINDS:
+        for a in R.P4_SLOW_AT:
+            st, r, lst = res[f"slow:{w},{a}"]
+            assert len(lst) == 70 and (lst[a][0] == "U" or lst[a][1] == by[f"slow:{w},{a}"] or lst[a][2] == R.P4_DEAD
+                                       or w == "absent")
+            assert (len(r["gossips"]) == 1) == w.startswith("own") and (len(r["events"]) == 1) == (w in ("dead", "user"))
+    for o in (0, 62):
+        st, r, lst = res[f"triple:timer,{o}"]
+        assert r["W"] == 3 and r["M"] == 2 and len(lst) == o + 3
+        assert st["row"][lst[-1][1]][3] == 1 + 5 * (N - 2).bit_length() * 10  # a new timer, at the size after the removals
+        assert res[f"triple:notimer,{o}"][1]["W"] == 3 and res[f"triple:notimer,{o}"][1]["M"] == 1
+    assert res["killed:"][1]["LOST"] == 4 and res["killed:"][1]["M"] == 5 and res["incs:"][1]["W"] >= 8 and not res["incs:"][1]["einc"]
+    if N == 66:  # a removal inside the list takes the table from 64 to 63 records: later timers use ceilLog2 = 6
+        for name in ("slow:dead,0", "slow2:", "mixed:100"):
+            assert {row[3] for row in res[name][0]["row"].values()} >= {5 * 7 * 10, 1 + 5 * 6 * 10}, name
+    assert R.p4_fold(R.p4_member(3, N, [], []), 0, 0, R.p4_case_einc(N)["ticks"][0][3][1], set(), cfg)["einc"]
