@@ -196,6 +196,7 @@ int swim_shard_range(swim_handle* h, uint32_t* lo, uint32_t* hi) {
 
 int swim_destroy(swim_handle* h) {
   if (!h) return SWIM_EINVAL;
+  watch_free_all(h);  // (a group's watches before its shards: they hold the shards' parts)
   if (h->grp) {
     group_destroy(h);
     return SWIM_OK;

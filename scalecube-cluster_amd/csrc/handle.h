@@ -7,6 +7,7 @@
 //   group.hip     swim_config.n_gpus > 1: one handle over several shard handles
 //   api.hip       the other extern "C" entry points: fault injection, readback
 //   debug_receipts.hip  swim_debug_receipts_set / _read: injected P4 receipts (tests)
+//   watch.hip     swim_watch_* / swim_run_until: the subject watch, its kernel included
 // The device side (engine.h, spec.h, dev_util.h): member.hip (member control: triage, phases, k_member_tick_t) over
 // member_state.h (a member's state, row writes, SYNC sends) and member_proto.h (the protocol handlers), inbox.hip
 // (k_inbox_apply: P4 of a parked member on one wave), user_gossip.hip (host-queued gossips, churn), sync_diff.hip (SYNC
@@ -28,6 +29,7 @@
 #include "engine.h"
 
 struct Group;  // group.hip
+struct swim_watch;  // watch.hip
 
 struct swim_handle {
   swim_config cfg;
@@ -107,6 +109,7 @@ struct swim_handle {
   std::vector<uint32_t> dbg_slots;
   uint64_t dbg_tick = 0;
   bool dbg_armed = false;
+  std::vector<swim_watch*> watches;  // the handle's live watches (swimhip_watch.h): swim_destroy frees what is left
   Group* grp = nullptr;  // n_gpus > 1: every call is forwarded to the shards (d holds shard 0's constants only)
 };
 
@@ -181,6 +184,8 @@ int prof_accumulate(swim_handle* h, uint64_t first, uint32_t n);
 int create_group(const swim_config* cfg, swim_handle** out);
 int group_step(swim_handle* h, uint32_t n);
 void group_destroy(swim_handle* h);
+// watch.hip
+void watch_free_all(swim_handle* h);
 
 #pragma GCC visibility pop
 }  // namespace swim

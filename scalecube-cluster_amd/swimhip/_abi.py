@@ -215,6 +215,46 @@ def bind_census(lib):
     return lib
 
 
+# include/swimhip_watch.h (the subject watch; exported by libswimhip only, not by the oracle)
+WATCH_MAX_SUBJECTS, WATCH_NEVER, WATCH_STAMPS, WATCH_BLOCK_ROWS = 256, 0xFFFFFFFF, 1, 256
+STAMP_NOT_ALIVE, STAMP_GONE, STAMP_INC_GE = 0, 1, 2
+STAMP_NAMES = ["not_alive", "gone", "inc_ge"]
+UNTIL_CONVERGED, UNTIL_NOT_ALIVE, UNTIL_GONE, UNTIL_INC_GE = 0, 1, 2, 3
+
+
+class SwimWatchSample(C.Structure):
+    _fields_ = [
+        ("tick", C.c_uint64),
+        ("n_observers", C.c_uint64),
+        ("counts", _U32P),
+        ("key_min", _U32P),
+        ("key_max", _U32P),
+        ("path", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+_W = C.c_void_p
+WATCH_SIGNATURES = {
+    "swim_watch_create": (C.c_int, [_H, _U32P, C.c_uint32, _U32P, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(_W)]),
+    "swim_watch_destroy": (C.c_int, [_W]),
+    "swim_watch_sample": (C.c_int, [_W, C.POINTER(SwimWatchSample)]),
+    "swim_watch_stamps": (C.c_int, [_W, C.c_uint32, _U32P, C.c_size_t]),
+    "swim_watch_met": (C.c_int, [C.c_uint32, C.c_uint32, _U32P, _U32P, _U32P, _U32P]),
+    "swim_run_until": (C.c_int, [_H, _W, C.c_uint32, C.c_uint32, C.c_uint32, _U32P, _U32P,
+                                 C.POINTER(SwimWatchSample)]),
+}
+
+
+def bind_watch(lib):
+    """Attach the watch entry points (engine library only)."""
+    for name, (res, args) in WATCH_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 # include/swimhip_selftest.h (known-answer surface; exported by libswimhip and by the oracle)
 SELFTEST_OVERRIDES, SELFTEST_PHILOX, SELFTEST_CLUSTER_MATH, SELFTEST_LOSS_ROLL = 0, 1, 2, 3
 SELFTEST_SIGNATURES = {

@@ -84,6 +84,9 @@ class SimulatedCluster:
     # -- lifecycle ------------------------------------------------------------------------------------------
     def close(self):
         if self._h:
+            for w in getattr(self, "_watches", ()):  # swim_destroy frees the handle's remaining watches
+                w._orphan()
+            self._watches = []
             self.lib.swim_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -255,6 +258,21 @@ class SimulatedCluster:
         rc, out = view_census(self.lib, self._h, self.n, observers, by_subject, by_observer, keys)
         self._ck(rc, "swim_view_census")
         return out
+
+    def watch(self, subjects, inc_target=None, observers=None, stamps=True):
+        """A swimhip.watch.Watch on up to 256 subjects (include/swimhip_watch.h; engine only): sample() tallies their
+        columns over every running member, or over the observers flagged in `observers` (n flags, copied), and stamps
+        each observer's first-seen ticks. inc_target: one incarnation per subject for the INC_GE stamp and condition."""
+        from .watch import Watch
+        w = Watch(self.lib, self._h, self.n, subjects, inc_target, observers, stamps, check=self._ck)
+        self.__dict__.setdefault("_watches", []).append(w)
+        return w
+
+    def run_until(self, watch, cond, max_ticks, check_every=1):
+        """Step until `cond` (_abi.UNTIL_*) holds for every subject of `watch`, looking every check_every ticks, for at
+        most max_ticks ticks: (met, ticks_run). awaitUntil(assertSuspected / assertRemoved ...) of the reference's tests."""
+        ok, ticks, _ = watch.run_until(self._h, cond, max_ticks, check_every)
+        return ok, ticks
 
     def counters(self):
         c = _abi.SwimCounters()

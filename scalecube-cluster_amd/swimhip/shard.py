@@ -337,6 +337,28 @@ class ThreadShardGroup:
             return self.shards[0].census(observers, by_subject, by_observer, keys)
         return combine([s.census(observers, by_subject, by_observer, keys) for s in self.shards])
 
+    def watch(self, subjects, inc_target=None, observers=None, stamps=True):
+        """One watch per row shard behind a swimhip.watch.GroupWatch: samples and stamps are the shards' combined."""
+        from .watch import GroupWatch
+        if self.slots:
+            raise SwimError("a watch needs MODE_FULL: RUMOR views never change")
+        return GroupWatch([s.watch(subjects, inc_target, observers, stamps) for s in self.shards])
+
+    def run_until(self, watch, cond, max_ticks, check_every=1):
+        """SimulatedCluster.run_until over the shards: sample per shard, combine, step all shards, in Python (one shard
+        cannot give the verdict alone: swim_run_until refuses it)."""
+        if check_every < 1:
+            raise ValueError("check_every must be at least 1")
+        done = 0
+        while True:
+            if watch.met(cond):
+                return True, done
+            if done >= max_ticks:
+                return False, done
+            n = min(check_every, max_ticks - done)
+            self.step(n)
+            done += n
+
     def counters(self):
         cs = [s.counters() for s in self.shards]
         return {k: (sum(c[k] for c in cs) if k != "tick" else cs[0][k]) for k in cs[0]}
