@@ -239,7 +239,7 @@ int swim_debug_dirty_check(swim_handle* h, uint64_t* violations);
  *            fetches the rest first) unless the gate stops the launch; an mtmp entry with src or dst >= N; rtail - rhead >
  *            BCAP; sizes out of the ranges above
  *
- * The gossip data plane's per-tick kernels (gossip.hip): the engine's own launchers, unchanged and in their
+ * The gossip data plane's per-tick kernels (gossip_*.hip): the engine's own launchers, unchanged and in their
  * own grids, for one tick k on a caller-built holder state, on a zeroed Dev that holds only what their kernels read and a
  * device copy of it (Dev::self). Scope: one GPU (W = XW = 1, lo = 0, hi = N); no link delays (dly_on = 0: the k_gossip_due*
  * kernels are not launched); exp = 0, dbg_send = null, fastp4 = 0; one settings epoch (ep_from[0] = 0, the others NEVER) and

@@ -196,7 +196,7 @@ static int fill_dev(swim_handle* h) {
   // a gossip's holders have all swept it within 2 (spread + 1) + 2 of their rounds after their receipt
   // (sweepGossips :283-308, spread <= maxSpread): its slot is recycled after that (slot_exp)
   d.EXPB = (2u * maxSpread + 4u) * d.gossip_t;
-  if (2u * maxSpread + 4u >= 500u) {  // receipt-ring entries keep the infection period modulo 1024 (gossip.hip)
+  if (2u * maxSpread + 4u >= 500u) {  // receipt-ring entries keep the infection period modulo 1024 (dev_util.h rg_entry)
     h->err = "gossipRepeatMult x ceilLog2(members) too large (at most 248)";
     return SWIM_EINVAL;
   }

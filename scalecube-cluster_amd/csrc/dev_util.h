@@ -189,6 +189,19 @@ __device__ __forceinline__ uint32_t gossip_arrival(const Dev& d, uint32_t src, u
 // the latest a send can arrive past tick + lat
 __device__ __forceinline__ uint32_t dmax(const Dev& d) { return d.dly_on ? d.EMAX : 0u; }
 
+// Exchange B (W > 1): what this shard's sends of the tick change in the holder state every shard replicates, one record
+// (slot, word) each: a first receipt of slot g by target t, or XD_EXT | tick for a delayed send that keeps the slot
+// (k_unpack_b applies them on the other shards). xd_put: the record at a place the caller reserved on xd_n.
+__device__ __forceinline__ void xd_put(const Dev& d, uint32_t xi, uint32_t g, uint32_t w) {
+  if (xi < d.DCAP)
+    d.xd[xi] = ((uint64_t)g << 32) | w;
+  else
+    set_err(d, E_DELIV);
+}
+__device__ __forceinline__ void xd_push(const Dev& d, uint32_t g, uint32_t w) {
+  if (d.W > 1) xd_put(d, atomicAdd(d.xd_n, 1u), g, w);
+}
+
 // a first-receipt candidate delayed past the next tick: queued by its delivery tick (k_gossip_due delivers it then);
 // its slot lives until every holder it makes has swept it
 __device__ __forceinline__ void delay_push(const Dev& d, uint32_t g, uint32_t t, uint32_t due) {
@@ -198,13 +211,7 @@ __device__ __forceinline__ void delay_push(const Dev& d, uint32_t g, uint32_t t,
   else
     set_err(d, E_DELAYQ);
   atomicMax(&d.slot_exp[g], due + d.EXPB);
-  if (d.W > 1) {  // the other shards extend the slot's life the same way (exchange B: XD_EXT record, k_unpack_b)
-    const uint32_t xi = atomicAdd(d.xd_n, 1u);
-    if (xi < d.DCAP)
-      d.xd[xi] = ((uint64_t)g << 32) | XD_EXT | due;
-    else
-      set_err(d, E_DELIV);
-  }
+  xd_push(d, g, XD_EXT | due);  // the other shards extend the slot's life the same way (k_unpack_b)
 }
 
 // the same with the settings epoch of tick k already looked up (epoch_at once per thread, not per message)
@@ -263,7 +270,7 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t* ctr) {
   return base + rank;
 }
 
-// the wave's sum (u32, and u64 as two 32-bit shuffles per step) and minimum of a value every lane holds
+// the wave's sum (u32, and u64 as two 32-bit shuffles per step), minimum and maximum of a value every lane holds
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -280,6 +287,22 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o));
+  return v;
+}
+
+// the wave's inclusive prefix sum: lane l gets the sum of v over the lanes 0..l (wave_reserve and block_reserve keep
+// the loop written out: through this function their callers come out with another register allocation)
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t o = 1; o < 64; o <<= 1) {
+    const uint32_t u = __shfl_up(v, o);
+    if (lane >= o) v += u;
+  }
   return v;
 }
 
@@ -457,7 +480,7 @@ __device__ __forceinline__ void s_put(const Dev& d, uint32_t g, uint32_t m, uint
   d.S[s_idx(d, g, m)] = (uint16_t)(S16_EVER | (ctick & S16_TICK) | (reborn ? S16_REBORN : 0u));
 }
 
-// ---- gossip holder state (gossip.hip) ----
+// ---- gossip holder state (the gossip plane: gossip_dev.h) ----
 // ring entries: slot (22 bits) | infection period & 1023 << 22. At a round every entry's period lies in
 // [P - 2 spreadMax - 3, P] (swim_create bounds spreadMax), so the low 10 bits identify it.
 constexpr uint32_t RG_SLOT = (1u << 22) - 1u;

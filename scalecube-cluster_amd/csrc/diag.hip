@@ -1,5 +1,6 @@
 // diag.hip — what swim_step prints and measures besides stepping: the SWIM_STATS dump of a gossip tick, the SWIM_EXP
-// dumps after a step (tools/ parse some of these lines), and the SWIM_FLAG_PROFILE event bookkeeping.
+// dumps after a step (tools/ parse some of these lines), the SWIM_FLAG_PROFILE event bookkeeping, and the holder-state
+// readback of swim_debug_holders.
 #include "handle.h"
 
 #include <algorithm>
@@ -179,6 +180,29 @@ int prof_accumulate(swim_handle* h, uint64_t first, uint32_t n) {
     h->prof_ms[2] += ms;
   }
   return SWIM_OK;
+}
+
+// test surface (swim_debug_holders): per member of [first, first + n): its gossip count, the receipt-ring positions of
+// the first held entry and of the end, the popcount of its held-bit row, and the first receipts whose GOSSIP events the
+// next P4 folds (RUMOR mode without recorded events)
+__global__ void __launch_bounds__(256) k_dbg_holders(const Dev* __restrict__ dp, uint32_t first, uint32_t n, uint32_t* out) {
+  const Dev& d = *dp;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t m = first + i;
+    const unsigned long long* hb = d.HB + (size_t)m * d.QW;
+    uint32_t pop = 0;
+    for (uint32_t w = 0; w < d.QW; ++w) pop += (uint32_t)__popcll(hb[w]);
+    uint32_t* o = out + 5ull * i;
+    o[0] = d.held[m];
+    o[1] = d.rhead[m];
+    o[2] = d.rtail[m];
+    o[3] = pop;
+    o[4] = d.evp_n ? d.evp_n[m] : 0u;
+  }
+}
+void launch_dbg_holders(const Dev& d, uint32_t first, uint32_t n, uint32_t* out, void* stream) {
+  hipLaunchKernelGGL(k_dbg_holders, dim3(std::min<uint32_t>(4096, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     d.self, first, n, out);
 }
 
 }  // namespace swim

@@ -69,7 +69,8 @@ constexpr uint32_t CIN_SLOW = 0xFFFFFFFEu;
 constexpr uint32_t RX_ALL = 0xFFFFFFFFu;
 constexpr uint32_t MDU = 64;  // members with updated metadata per handle
 // cached contact events per (sender, target): n, oldest[2], last inbound, then per event tick, slot | dir | loss % |
-// spread, and the sender's rounds before the event's tick
+// spread, and the sender's rounds before the event's tick (the one encoder and decoder, with the field widths: cev_put
+// and cev_get beside the device-side Contact, gossip_replay.h)
 constexpr uint32_t CEV = 6, CEVW = 4 + 3 * CEV;
 // gossip incarnation history entry: 3 header words + HKEEP creation ticks of swept incarnations (small clusters
 // under loss re-infect a member with the same gossip many times: each late sender restarts the chain)
@@ -262,7 +263,7 @@ struct Dev {
   uint32_t* cev;  // [N][F][CEVW] contact events of (m, T[m][s]) cached by k_gossip_contacts when tcontact is set
   uint32_t *log_tick, *log_spread, *log_cnt, *log_tg, *log_pos;  // [N][LOGW], tg [N][LOGW][F], pos [N]
 
-  // ---- holder state (gossip.hip) ----
+  // ---- holder state (gossip_dev.h) ----
   // Bit planes indexed by slot id, member-major: HB = held (GossipProtocolImpl.gossips contains the id), kept up to
   // date by every creation, first receipt and sweep; WB = inside the member's spread window as of its latest round
   // (selectGossipsToSend :239-250), rebuilt incrementally at each of its rounds. QW = SLOTS / 64 words per row.
@@ -589,8 +590,8 @@ struct GossipChunks {
   uint32_t cw, cb, cx;
 };
 void launch_gossip_send(const Dev& d, uint32_t k, hipStream_t st, const TickEvents* prof,
-                        const GossipChunks* chunks = nullptr);  // gossip.hip
-void launch_gossip_apply(const Dev& d, uint32_t k, hipStream_t st);
+                        const GossipChunks* chunks = nullptr);  // gossip_send.hip
+void launch_gossip_apply(const Dev& d, uint32_t k, hipStream_t st);  // gossip_apply.hip
 void launch_unpack_b(const Dev& d, uint32_t k, hipStream_t st);
 void launch_scan(const uint32_t* in, uint32_t* out, uint32_t* part, uint32_t n, hipStream_t st);  // route.hip
 void launch_receipt_routing(const Dev& d, hipStream_t st);

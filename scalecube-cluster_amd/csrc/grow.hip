@@ -42,6 +42,40 @@ static int grow_lists(swim_handle* h, uint64_t rcap, uint64_t pcap, uint64_t* bu
   return SWIM_OK;
 }
 
+// every entry of the incarnation history re-inserted into a table of cap2 entries (same probing as hist_push,
+// gossip_dev.h: linear from its tag)
+__global__ void __launch_bounds__(256) k_hist_rehash(const uint64_t* h1, uint32_t cap1, uint64_t* h2, uint32_t cap2) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cap1; i += gridDim.x * blockDim.x) {
+    const uint64_t* e = h1 + (size_t)i * HREC;
+    const uint64_t tag = e[0];
+    if (!tag) continue;
+    for (uint32_t p = 0; p < cap2; ++p) {
+      unsigned long long* o = (unsigned long long*)(h2 + (size_t)((tag + p) & (cap2 - 1)) * HREC);
+      if (atomicCAS(o, 0ull, (unsigned long long)tag) != 0ull) continue;
+      for (uint32_t j = 1; j < HREC; ++j) o[j] = e[j];
+      break;
+    }
+  }
+}
+void launch_hist_rehash(const uint64_t* h1, uint32_t cap1, uint64_t* h2, uint32_t cap2, void* stream) {
+  hipLaunchKernelGGL(k_hist_rehash, dim3(2048), dim3(256), 0, (hipStream_t)stream, h1, cap1, h2, cap2);
+}
+
+// member m's held ring entries [rhead, rtail) at their positions in a ring of B2 entries (positions are absolute; a
+// ring of B entries keeps position p at p & (B - 1))
+__global__ void __launch_bounds__(256) k_ring_move(const uint32_t* rg, uint32_t* rg2, const uint32_t* rhead,
+                                                   const uint32_t* rtail, uint32_t N, uint32_t B, uint32_t B2) {
+  for (uint32_t m = blockIdx.x; m < N; m += gridDim.x) {
+    const uint32_t h = rhead[m], t = rtail[m];
+    for (uint32_t p = h + threadIdx.x; p - h < t - h; p += blockDim.x)
+      rg2[(size_t)m * B2 + (p & (B2 - 1))] = rg[(size_t)m * B + (p & (B - 1))];
+  }
+}
+void launch_ring_move(const uint32_t* rg, uint32_t* rg2, const uint32_t* rhead, const uint32_t* rtail, uint32_t N,
+                      uint32_t B, uint32_t B2, void* stream) {
+  hipLaunchKernelGGL(k_ring_move, dim3(4096), dim3(256), 0, (hipStream_t)stream, rg, rg2, rhead, rtail, N, B, B2);
+}
+
 // incarnation history: a larger table, every entry re-inserted
 static int grow_history(swim_handle* h, uint64_t hcap2, uint64_t* budget, bool* grew) {
   Dev& d = h->d;

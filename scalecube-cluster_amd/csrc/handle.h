@@ -11,8 +11,9 @@
 // The device side (engine.h, spec.h, dev_util.h): member.hip (member control: triage, phases, k_member_tick_t) over
 // member_state.h (a member's state, row writes, SYNC sends) and member_proto.h (the protocol handlers), inbox.hip
 // (k_inbox_apply: P4 of a parked member on one wave), user_gossip.hip (host-queued gossips, churn), sync_diff.hip (SYNC
-// diff and its lister), sync_delay.hip (delayed-SYNC store), route.hip (receipt routing), gossip.hip (gossip data
-// plane), shard.hip (row-shard pack / unpack), kernels.hip (initialisation, state hashes, the tick launchers; the
+// diff and its lister), sync_delay.hip (delayed-SYNC store), route.hip (receipt routing), gossip_round.hip /
+// gossip_contacts.hip / gossip_send.hip / gossip_apply.hip (the gossip data plane by stage, over gossip_dev.h and
+// gossip_replay.h: the file map is in gossip_dev.h), shard.hip (row-shard pack / unpack), kernels.hip (initialisation, state hashes, the tick launchers; the
 // member kernels it launches are declared in member_kernels.h).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // kernels.hip — initialisation, state hashes, the small between-tick kernels and the tick launchers (the SYNC diff is
 // in sync_diff.hip, the delayed-SYNC store in sync_delay.hip, receipt routing in route.hip, the gossip data plane in
-// gossip.hip).
+// gossip_*.hip).
 #include <hip/hip_runtime.h>
 
 #include "dev_util.h"
@@ -57,7 +57,7 @@ __global__ void k_init_members(Dev d) {
   d.m_head[m] = d.m_head[d.N + m] = NEVER;
   d.next_evt[m] = NEVER;
   d.pending_inc[m] = 0;
-  d.rhead[m] = d.rwin[m] = d.rseen[m] = d.rtail[m] = 0;  // empty receipt ring (gossip.hip)
+  d.rhead[m] = d.rwin[m] = d.rseen[m] = d.rtail[m] = 0;  // empty receipt ring (gossip_dev.h)
   d.tin_cnt[m] = d.tin_fill[m] = 0;
   if (m >= d.lo && m < d.hi)
     for (uint32_t g = 0; g < d.GRCAP; ++g) d.groups[(lidx(d, m) * d.GRCAP + g) * GREC + 5] = 0;

@@ -3,7 +3,7 @@
 // This kernel is the control plane of the protocol stack of every member: FailureDetectorImpl, MembershipProtocolImpl,
 // MetadataStoreImpl and the selection half of GossipProtocolImpl. Its work per member per tick is O(1) in the
 // common case. The O(N) work runs elsewhere: the SYNC-payload diff (k_sync_diff) and the gossip data plane
-// (gossip.hip). Remote hops of stateless request handlers (onPing, onPingReq, onTransitPingAck,
+// (gossip_*.hip). Remote hops of stateless request handlers (onPing, onPingReq, onTransitPingAck,
 // onMetadataRequest) are evaluated at the issuer, at the hop's own tick and against that tick's network
 // settings. The payload they would carry is only the correlation id, so no message is materialised.
 //
@@ -454,7 +454,7 @@ __device__ __forceinline__ void p3_metadata(ML& L, bool dead) {
 }
 
 // ---- P4 gossip first receipts in gossip-id order -> onMembershipGossip (:401-408) ----
-// only the receipts that can change the row were routed (receipt_matters, gossip.hip); the others were counted
+// only the receipts that can change the row were routed (receipt_matters, gossip_apply.hip); the others were counted
 // as record compares by the triage. off, n: the member's routed receipts (Dev::rc_off, rc_cnt)
 __device__ __forceinline__ void p4_receipts(ML& L, uint32_t off, uint32_t n) {
   const Dev& d = *L.d;

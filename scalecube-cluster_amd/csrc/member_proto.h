@@ -498,7 +498,7 @@ __device__ __forceinline__ void do_ping(ML& L) {
 
 // ---- GossipProtocolImpl, the selection half ----
 // doSpreadGossip (GossipProtocolImpl.java:139-157) target selection (:252-273). The sends and the sweep run in
-// the gossip data plane (gossip.hip) from T / tspread / tperiod; the round is logged for infectedFrom replay.
+// the gossip data plane (gossip_round.hip on) from T / tspread / tperiod; the round is logged for infectedFrom replay.
 __device__ __forceinline__ void do_spread_gossip(ML& L) {
   const Dev& d = *L.d;
   if (L.held == 0) return;

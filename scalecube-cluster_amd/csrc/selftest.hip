@@ -2,7 +2,7 @@
 // evaluated on caller inputs in a gfx950 kernel, so the reference's known answers pin the device code itself; and
 // swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives and the SYNC diff with its
 // lister the same way, and the row-shard exchange codec (shard.hip) and the gossip data plane's per-tick kernels
-// (gossip.hip) in the engine's own grids (engine only).
+// (gossip_*.hip) in the engine's own grids (engine only).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,7 +75,7 @@ extern "C" int swim_selftest_eval(uint32_t op, const uint32_t* in, uint32_t* out
 
 // ------------------------------------------------------------------------------------------------------------
 // swim_debug_prim_eval (include/swimhip_debug.h): the routing, wave and window primitives on caller data. Every kernel
-// here only calls the engine's own functions (dev_util.h, engine.h, swim_common.h, route.hip, gossip.hip); the host
+// here only calls the engine's own functions (dev_util.h, engine.h, swim_common.h, route.hip, grow.hip); the host
 // side checks every size and index first, so no input reaches a kernel that could index out of an allocation.
 namespace swim {
 

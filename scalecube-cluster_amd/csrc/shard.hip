@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(256) k_unpack_a(Dev d, uint32_t k, uint32_t en
 }
 
 // this shard's first receipts of the tick (its targets' senders ran here): every peer applies them to its replicated
-// holder state (gossip.hip k_unpack_b)
+// holder state (gossip_apply.hip k_unpack_b)
 __global__ void __launch_bounds__(256) k_pack_b(Dev d) {
   const uint32_t q = blockIdx.y;
   if (q == d.rank) return;

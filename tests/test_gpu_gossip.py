@@ -1,4 +1,4 @@
-"""Known answers for the gossip data plane's per-tick kernels (gossip.hip) through SWIM_PRIM_GOSSIP of
+"""Known answers for the gossip data plane's per-tick kernels (gossip_round.hip to gossip_apply.hip) through SWIM_PRIM_GOSSIP of
 swim_debug_prim_eval (include/swimhip_debug.h): launch_gossip_send and launch_gossip_apply run unchanged, in their own
 grids, for one tick on a holder state built by tests/prim_ref.py, every output preset to a sentinel, and what they leave is
 compared with the plain references there (gs_ref: Python sets of slot ids per member; validated without a GPU in

@@ -122,7 +122,7 @@ def run_wave(engine, sub, a, ctr0=0):
     return out[:3 * T].reshape(3, T), int(out[3 * T])
 
 
-# wave_append inside a divergent branch (k_scatter_rc's `f == 1`, the list builders of gossip.hip)
+# wave_append inside a divergent branch (k_scatter_rc's `f == 1`, the list builders of the gossip plane)
 @pytest.mark.parametrize("pat", list(PATTERNS))
 def test_wave_append(engine, pat):
     act = PATTERNS[pat]
