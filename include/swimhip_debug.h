@@ -101,6 +101,31 @@ int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc);
 #define SWIM_DD_LF_STOPS 9u     /* lister-free batches stopped because a member kernel wrote */
 int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n);
 
+/* One GPU, FULL mode, stored tables: the member kernel runs the steady state's member-ticks (a ping, its hop, its ack,
+ * one or two SYNC / SYNC_ACK receipts with nothing to merge, the periodic SYNC send) on a light path that loads what it
+ * needs in rounds of independent loads, decides in registers, and commits only then; anything else falls back, before
+ * any store, to the general body, which is also its reference ("Round 12"). SWIM_NO_LIGHT=1 (any value
+ * but 0), read by swim_create, runs every member-tick through the general body. That is the tests' reference path, not
+ * the kernel as it was before the path existed: the launch keeps the path's LDS lists, so timing against that kernel
+ * needs both builds. The path is also off while link delays or per-link settings exist.
+ * swim_debug_light: n <= 13 entries since create. SWIM_LT_GENERAL is counted while the path is on, and with it off
+ * only on a handle that counts its fallbacks (SWIM_CAPS / SWIM_FALLBACKS at create), so that a handle without the path
+ * pays nothing for it. A multi-device or sharded handle: SWIM_EUNSUPPORTED. */
+#define SWIM_LT_TICKS 0u          /* member-ticks finished by the light path */
+#define SWIM_LT_FD 1u             /* of them with a ping, a ping hop or an ack arrival */
+#define SWIM_LT_P1 2u             /* of them with a SYNC / SYNC_ACK receipt */
+#define SWIM_LT_SYNC 3u           /* of them with the periodic SYNC send */
+#define SWIM_LT_GENERAL 4u        /* member-ticks run by the general body (the fallbacks among them) */
+#define SWIM_LT_FB_RESHUFFLE 5u   /* fallbacks by reason: the ping cursor reached the end of the list */
+#define SWIM_LT_FB_SEND 6u        /* the ping's send failed (a ping-req follows) */
+#define SWIM_LT_FB_PAYLOADS 7u    /* three inbound SYNC / SYNC_ACK payloads or more (two under SWIM_CAPS mq=1) */
+#define SWIM_LT_FB_CAND 8u        /* a payload with records to merge */
+#define SWIM_LT_FB_BUSY 9u        /* pending fetches, several paths or subscriptions, a ping-req's */
+#define SWIM_LT_FB_STATUS 10u     /* an ack for a target the row holds as neither ALIVE nor ABSENT (a SYNC follows) */
+#define SWIM_LT_FB_OTHER 11u
+#define SWIM_LT_ON 12u            /* 1: the next member kernel takes the light path, 0: it does not */
+int swim_debug_light(swim_handle* h, uint64_t* out, size_t n);
+
 /* the masks' invariant, tested directly: the number of (row, chunk) pairs marked clean whose keys differ from the
  * baseline's chunk, which on one GPU is what the first row marked clean in that chunk holds: all clean rows must agree
  * (0 in a correct engine). One pass over the key plane. */

@@ -273,6 +273,13 @@ static int fill_dev(swim_handle* h) {
     d.MW = kp.MW;
     if (d.ackres && !getenv("SWIM_NO_DIRTY")) d.ackres |= ACKRES_DIRTY;
   }
+  // the member kernel's light path (member_light.h): one GPU, FULL mode, stored tables, no timing experiment that laps
+  // the general body's phases. SWIM_NO_LIGHT (any value but 0) turns it off: the tests' reference path. (Not the
+  // parent kernel of the round that added the path: the launch keeps its LDS lists, so an A/B against that needs both builds.)
+  if (d.W == 1 && d.XW == 1 && !d.implicit && d.mode != SWIM_MODE_RUMOR && !(d.exp & ~LIGHT_EXP_OK)) {
+    const char* nl = getenv("SWIM_NO_LIGHT");
+    d.light = nl && strcmp(nl, "0") ? 0u : LIGHT_ON;
+  }
   if (d.W > 1) {
     d.MW = kp.MW;
     d.NSCAP = 1u << 16;

@@ -3,6 +3,8 @@
 // readback of swim_debug_holders.
 #include "handle.h"
 
+#include "../../include/swimhip_debug.h"
+
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -181,6 +183,27 @@ int prof_accumulate(swim_handle* h, uint64_t first, uint32_t n) {
   }
   return SWIM_OK;
 }
+
+}  // namespace swim
+
+// test surface (swim_debug_light): the light path's counters, summed over the member kernel's counter rows, and whether
+// the next launch takes the path (the device-side rule: member_light.h light_mode)
+extern "C" int swim_debug_light(swim_handle* h, uint64_t* out, size_t n) {
+  if (!h || !out || n > SWIM_LT_ON + 1) return SWIM_EINVAL;
+  if (h->grp || h->d.W > 1 || h->d.XW > 1) return SWIM_EUNSUPPORTED;
+  const Dev& d = h->d;
+  HIPCK(hipStreamSynchronize(h->stream));
+  std::vector<unsigned long long> sh((size_t)CSH * CSTRIDE);
+  HIPCK(hipMemcpy(sh.data(), d.ctr_sh, 8 * sh.size(), hipMemcpyDeviceToHost));
+  uint64_t v[SWIM_LT_ON + 1] = {};
+  for (uint32_t r = 0; r < CSH; ++r)
+    for (uint32_t i = 0; i < SWIM_LT_ON; ++i) v[i] += sh[(size_t)r * CSTRIDE + SH_LIGHT + i];
+  v[SWIM_LT_ON] = d.light && !d.dly_on && !d.link_n ? 1u : 0u;
+  for (size_t i = 0; i < n; ++i) out[i] = v[i];
+  return SWIM_OK;
+}
+
+namespace swim {
 
 // test surface (swim_debug_holders): per member of [first, first + n): its gossip count, the receipt-ring positions of
 // the first held entry and of the end, the popcount of its held-bit row, and the first receipts whose GOSSIP events the

@@ -98,7 +98,9 @@ constexpr uint32_t CSH = 64, CSTRIDE = 64;  // Dev::ctr_sh rows, 512 B apart
 // Every row's words SH_LF .. SH_LF + 2: what the receivers counted in the lister's place on ticks without a lister launch
 // (member.hip, lf_count): messages resolved, narrow messages decided without a stream, of those pinned; the host adds
 // them to C_ACKRES_ALL, to C_DIFFMSG_ALL and C_DMSGSKIP, and to the pinned count (api.hip lf_counts).
-constexpr uint32_t SH_LF = 8, SH_HALT = 16, SH_PINDEC = 32;
+// Every row's words SH_LIGHT .. SH_LIGHT + LT_N - 1 (a 128-B line of their own): what the member kernel's light path did
+// and what fell back to the general body (member_light.h LT_*; swim_debug_light sums the rows).
+constexpr uint32_t SH_LF = 8, SH_HALT = 16, SH_PINDEC = 32, SH_LIGHT = 48;
 enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29,
            // dirty-chunk skipping of the SYNC diff (one GPU): narrow 2048-subject chunks the lister had
            // streamed, their subjects over the timed and over all launches (2 B each in swim_counters.diff_key_bytes*),
@@ -389,6 +391,9 @@ struct Dev {
   uint32_t* dbg_send_n;
   uint32_t dbg_send_cap;
   uint32_t exp;  // timing experiments only (SWIM_EXP): the EXP_ bits of spec.h
+  // the member kernel's light path (member_light.h; LIGHT_ON, 0: every member-tick runs the general body):
+  // one-GPU FULL-mode handles with stored tables, unless SWIM_NO_LIGHT is set at create
+  uint32_t light;
   // runtime capacities of the fast structures (<= the compile-time sizes TRK, ULOG, CREQ, CWMAX, CEV, MQ, SORT_MAX);
   // SWIM_CAPS lowers them so that tests drive every exact fallback path (include/swimhip_debug.h)
   uint32_t trk_cap, ulog_cap, creq_cap, cwmax_cap, cev_cap, mq_cap, sort_cap;
@@ -469,6 +474,10 @@ static inline KeyPlaneSizes key_plane_sizes(uint32_t N) {
   return z;
 }
 
+constexpr uint32_t LIGHT_ON = 1;  // Dev::light
+// the SWIM_EXP bits the light path runs under: the per-wave wall clock and the class skips (the cycle laps are the
+// general body's)
+constexpr uint32_t LIGHT_EXP_OK = 512u | 32u | 64u;
 constexpr uint32_t ACKRES_ON = 1, ACKRES_DIRTY = 2;
 // one GPU with the dirty masks consulted and the 8-bit plane: the lister decides pinned live-row payloads from the
 // masks, and a speculative batch may queue no k_sync_diff on its untimed ticks (step.hip)

@@ -11,6 +11,7 @@
 // SEMANTICS.md §4) and the kernel. The member's state is in member_state.h, the handlers the phases call in
 // member_proto.h, P4 of a parked member on a wave of its own in inbox.hip.
 #include "member_kernels.h"
+#include "member_light.h"
 #include "member_proto.h"
 
 namespace swim {
@@ -21,8 +22,11 @@ namespace swim {
 // nothing else, 2 = only request-state events (ping hops, ack arrivals, timeouts), 3 = both, 0 = anything else (SYNC
 // receipt, gossip receipts or round, timers, host requests, start).
 // nolist: no lister ran for this tick (MT_NOLIST); lfc: what it would have counted for the payloads dropped here
+// light (member_light.h light_mode; 0: the classes above): a member whose causes the light path knows (an inbound SYNC
+// list, a request event, a ping, the periodic SYNC, an empty gossip round) gets class 1 (a list), 3 (a
+// ping or a SYNC due) or 2, everything that needs the general body class 0; head: its inbound list head, for that path
 __device__ __forceinline__ bool member_triage(const Dev& d, uint32_t m, uint32_t k, uint32_t& cls, uint32_t& drops,
-                                              uint32_t& evs, bool nolist, uint64_t& lfc) {
+                                              uint32_t& evs, bool nolist, uint64_t& lfc, uint32_t light, uint32_t& head) {
   // A dead member does nothing itself, but the remote hops of its in-flight requests still run at the live
   // responders (their sends fail against the dead issuer), so those hops are still evaluated for the counters.
   // every word is loaded up front (no short-circuit chain of dependent loads); the SoA loads coalesce per wave
@@ -69,6 +73,13 @@ __device__ __forceinline__ bool member_triage(const Dev& d, uint32_t m, uint32_t
     const bool other = (k > 0 && mh != NEVER) | (rc != 0) | (pi != 0) | (tm <= k) | ((inf & INIT_ACTIVE) != 0) |
                        (k == st) | (k == ng && held != 0);
     cls = other ? 0u : (k == np || k == ns ? 1u : 0u) | (ne <= k ? 2u : 0u);
+    if (light) {
+      const bool list = k > 0 && mh != NEVER;
+      const bool general = (rc != 0) | (pi != 0) | (tm <= k) | ((inf & INIT_ACTIVE) != 0) | (k == st) |
+                           (k == ng && held != 0);
+      cls = general ? 0u : list ? 1u : (k == np || k == ns) ? 3u : 2u;
+      head = list ? mh : NEVER;
+    }
     if (!busy) {
       if (k != ng) {
         d.tround[m] = 0;
@@ -697,6 +708,8 @@ __device__ __forceinline__ void member_tick_body(const Dev& d, uint32_t m, uint3
 // ping hop and an ack arrival, and no wave runs mostly idle lanes. Counters are summed across the wave first
 // (ctr_wave_add). With `flag` (W == 1) the block that finishes last runs the end-of-tick resets and raises the host
 // flag. flag: MT_END = W == 1 (end-of-tick work), MT_SPEC = a launch of a speculative batch (spec.h).
+// BODY_FULL on a one-GPU handle (light_mode): classes 1-3 are the members whose tick the light path knows
+// (member_light.h) and run it; class 0, and whatever a light lane cannot finish, runs the general body afterwards.
 // (MODE: BODY_FULL, or the two launches around k_inbox_apply, BODY_SPLIT and BODY_RESUME: three kernels, each with its
 // own register allocation, so the steady-state one keeps the code it had before the split)
 template <uint32_t MODE>
@@ -728,7 +741,15 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   const bool nolist = MODE == BODY_FULL && mt_nolist(flag);  // (a split tick is never queued without its lister)
   __shared__ uint64_t lfs[256];
   uint64_t lft = 0;
-  const bool busy = !resume && m < d.hi && member_triage(d, m, k, cls, drops, evs, nolist, lft);
+  // the light path (member_light.h): the launch's mode, and beside list[] each listed member's inbound list head (the
+  // triage's load) and the members whose light attempt fell back to the general body
+  uint32_t light = 0;
+  if constexpr (MODE == BODY_FULL) light = light_mode(d);
+  __shared__ uint32_t lhead[MODE == BODY_FULL ? 256 : 1], fbl[MODE == BODY_FULL ? 256 : 1];
+  __shared__ uint32_t fb_n;
+  if (MODE == BODY_FULL && threadIdx.x == 0) fb_n = 0;
+  uint32_t mhead = NEVER;
+  const bool busy = !resume && m < d.hi && member_triage(d, m, k, cls, drops, evs, nolist, lft, light, mhead);
   if (nolist) lfs[threadIdx.x] = lft;
   {  // the triage's record compares and folded RUMOR events, one atomic each per wave
     const uint32_t v = wave_sum(drops), e = wave_sum(evs);
@@ -758,6 +779,7 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   const uint64_t bal = cls == 0 ? b0 : cls == 1 ? b1 : cls == 2 ? b2 : b3;
   uint32_t slot = start + before + __popcll(bal & ((1ull << lane) - 1ull));
   if (busy) list[slot] = m | (cls << 30);  // m < 2^30
+  if (MODE == BODY_FULL && busy && light) lhead[slot] = mhead;
   __syncthreads();
   uint32_t ent = list[threadIdx.x];
   if (resume) {
@@ -772,12 +794,50 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
     if ((threadIdx.x & 63) == 0) wt[1] = wall_clock64() | (cm << 56) | ((uint64_t)nb << 48);
   }
   // SWIM_EXP & 32 / 64 (timing experiments, wrong results): skip the bodies of class 0 / of classes 1-3
-  if (__ballot(me != NEVER)) {  // waves with no busy member skip to the end
-    unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if constexpr (MODE != BODY_FULL) {
+    if (__ballot(me != NEVER)) {  // waves with no busy member skip to the end
+      unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      const bool skip = ((d.exp & EXP_SKIP_CLASS0) && mcls == 0) || ((d.exp & EXP_SKIP_CLASS123) && mcls != 0);
+      if (me != NEVER && !skip)
+        member_tick_body<MODE>(d, me, k, cnt, cw, &cw_n, spec1, nolist ? &lfs[threadIdx.x] : nullptr);
+      ctr_wave_add(d, cnt, lane);
+    }
+  } else {
+    // With the light path on, the waves of classes 1-3 try it first. Every member that needs the general body (class 0,
+    // and a light lane that must fall back: beside its wave's light lanes divergence would run both paths one after the
+    // other) is listed in LDS, and after a barrier the block's first lanes run the general body for the list: one call
+    // site, reached with nothing of the light path live. With it off the lanes run their own entries, as BODY_SPLIT.
     const bool skip = ((d.exp & EXP_SKIP_CLASS0) && mcls == 0) || ((d.exp & EXP_SKIP_CLASS123) && mcls != 0);
-    if (me != NEVER && !skip)
-      member_tick_body<MODE>(d, me, k, cnt, cw, &cw_n, spec1, nolist ? &lfs[threadIdx.x] : nullptr);
-    ctr_wave_add(d, cnt, lane);
+    uint32_t gm = skip ? NEVER : me;  // the member whose general body this lane runs
+    bool any = __ballot(me != NEVER) != 0ull;  // waves with no busy member skip to the end
+    if (light) {
+      if (any) {
+        unsigned long long lc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        uint32_t did = 0;  // the attempt's LT_ bits
+        bool gen = gm != NEVER && mcls == 0;
+        if (gm != NEVER && mcls != 0) {
+          did = member_light(d, gm, k, lhead[threadIdx.x], spec1, nolist ? &lfs[threadIdx.x] : nullptr, lc);
+          gen = (did & LT_FALLBACK) != 0u;
+        }
+        if (gen) fbl[wave_append(&fb_n)] = gm;  // (LDS)
+        if (__ballot(did != 0u)) {
+          ctr_wave_add(d, lc, lane);
+          light_count(d, did, lane);
+        }
+      }
+      if (wtime && (threadIdx.x & 63) == 0) wt[2] = wall_clock64();
+      __syncthreads();
+      gm = threadIdx.x < fb_n && !(d.exp & EXP_SKIP_CLASS0) ? fbl[threadIdx.x] : NEVER;
+      any = __ballot(gm != NEVER) != 0ull;
+    }
+    if (any) {
+      unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (gm != NEVER) member_tick_body<MODE>(d, gm, k, cnt, cw, &cw_n, spec1, nolist ? &lfs[threadIdx.x] : nullptr);
+      ctr_wave_add(d, cnt, lane);
+      // (counted with the path on, and for a handle that counts its fallbacks: the tests' reference path)
+      if (light || d.fb) light_count_general(d, gm != NEVER, lane);
+    }
+    if (!light && wtime && (threadIdx.x & 63) == 0) wt[2] = wall_clock64();
   }
   const uint64_t lfc = nolist ? lfs[threadIdx.x] : 0ull;
   if (nolist && __ballot(lfc != 0ull)) {  // (wave-uniform) into the block's counter row, as the op counters
@@ -788,7 +848,7 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
       if (lane == 0 && v) atomicAdd(&cs[i], (unsigned long long)v);
     }
   }
-  if (wtime && (threadIdx.x & 63) == 0) wt[2] = wall_clock64();
+  if (MODE != BODY_FULL && wtime && (threadIdx.x & 63) == 0) wt[2] = wall_clock64();  // (BODY_FULL: above)
   // deferred copy-on-write: the block copies each snapshot's row (final for this tick: only its member writes it),
   // then one lane undoes the member's logged writes since the snapshot opened, newest first
   __syncthreads();

@@ -287,6 +287,7 @@ DEBUG_SIGNATURES = {
     "swim_debug_set_incarnation": (C.c_int, [_H, C.c_uint32, C.c_uint32]),
     "swim_debug_diff_dirty": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
     "swim_debug_dirty_check": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
+    "swim_debug_light": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
     "swim_debug_prim_eval": (C.c_int, [C.c_uint32, _U32P, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_uint32]),
     "swim_debug_receipts_set": (C.c_int, [_H, _U32P, C.c_size_t, _U32P, C.c_size_t, C.c_uint32]),
@@ -404,6 +405,24 @@ def debug_diff_dirty(lib, handle, n=len(DD_NAMES)):
     if rc != 0:
         raise RuntimeError(f"swim_debug_diff_dirty rc={rc}")
     return dict(zip(DD_NAMES[:n], (int(x) for x in out)))
+
+
+# swim_debug_light's entries (include/swimhip_debug.h SWIM_LT_*)
+LIGHT_NAMES = ["ticks", "fd", "p1", "sync", "general", "fb_reshuffle", "fb_send", "fb_payloads", "fb_candidates",
+               "fb_busy", "fb_status", "fb_other", "on"]
+
+
+def debug_light(lib, handle):
+    """{name: count} of the member kernel's light path since create: member-ticks it finished (and those with an FD
+    case, a SYNC receipt, the periodic SYNC send), member-ticks of the general body, fallbacks by reason, and whether
+    the next launch takes the path (include/swimhip_debug.h swim_debug_light)."""
+    fn = lib.swim_debug_light
+    fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_light"]
+    out = (C.c_uint64 * len(LIGHT_NAMES))()
+    rc = fn(handle, out, len(LIGHT_NAMES))
+    if rc != 0:
+        raise RuntimeError(f"swim_debug_light rc={rc}")
+    return dict(zip(LIGHT_NAMES, (int(x) for x in out)))
 
 
 def debug_dirty_check(lib, handle):
