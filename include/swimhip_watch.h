@@ -30,6 +30,9 @@
  *
  * The watch's device memory is its own allocation, made once at create and reused by every sample; it is not part of
  * swim_counters.device_bytes. swim_destroy frees the handle's remaining watches.
+ *
+ * A sample is a host call between two steps. swimhip_watch_series.h arms a recording instead: the engine takes the
+ * samples itself behind the ticks inside swim_step and keeps them as a series.
  */
 #ifndef SWIMHIP_WATCH_H
 #define SWIMHIP_WATCH_H

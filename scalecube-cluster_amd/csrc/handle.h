@@ -7,7 +7,7 @@
 //   group.hip     swim_config.n_gpus > 1: one handle over several shard handles
 //   api.hip       the other extern "C" entry points: fault injection, readback
 //   debug_receipts.hip  swim_debug_receipts_set / _read: injected P4 receipts (tests)
-//   watch.hip     swim_watch_* / swim_run_until: the subject watch, its kernel included
+//   watch.hip     swim_watch_* / swim_run_until: the subject watch, its kernel and its recording included
 // The device side (engine.h, spec.h, dev_util.h): member.hip (member control: triage, phases, k_member_tick_t) over
 // member_state.h (a member's state, row writes, SYNC sends) and member_proto.h (the protocol handlers), inbox.hip
 // (k_inbox_apply: P4 of a parked member on one wave), user_gossip.hip (host-queued gossips, churn), sync_diff.hip (SYNC
@@ -111,6 +111,9 @@ struct swim_handle {
   uint64_t dbg_tick = 0;
   bool dbg_armed = false;
   std::vector<swim_watch*> watches;  // the handle's live watches (swimhip_watch.h): swim_destroy frees what is left
+  // those of them with a recording armed (swimhip_watch_series.h): step.hip queues their samples where a tick comes to
+  // rest (watch_tick_done); empty unless a recording is armed
+  std::vector<swim_watch*> recording;  // (a full series leaves it at the next swim_step's start)
   Group* grp = nullptr;  // n_gpus > 1: every call is forwarded to the shards (d holds shard 0's constants only)
 };
 
@@ -187,6 +190,15 @@ int group_step(swim_handle* h, uint32_t n);
 void group_destroy(swim_handle* h);
 // watch.hip
 void watch_free_all(swim_handle* h);
+int watch_record_tick(swim_handle* h, uint32_t t, bool in_batch, bool lf);
+void watch_record_prune(swim_handle* h);
+// The state at rest at tick t exists once everything queued so far has run: the armed recordings' samples of t go
+// behind it. in_batch: queued inside a speculative batch (lf: a lister-free one), where the launches before it may
+// return at once: the sample then reads the halt words (spec.h halted_sample) and the host queues it again where it
+// resumes. No recording armed: nothing is queued.
+inline int watch_tick_done(swim_handle* h, uint32_t t, bool in_batch, bool lf) {
+  return h->recording.empty() ? SWIM_OK : watch_record_tick(h, t, in_batch, lf);
+}
 
 #pragma GCC visibility pop
 }  // namespace swim

@@ -19,6 +19,8 @@
 //   k_sync_defer<true>                halted_uncommitted    hg != 0 && hg <= k + 1
 //   k_pack_all, k_unpack_a,           halted                hg != 0
 //   k_inline_in
+//   k_watch (a recorded sample of     halted_sample         hg != 0 && hg <= t, or hd != 0; lister-free: or hw != 0 &&
+//   tick t, behind member(t - 1))                           hw <= t - 1
 //
 // Why the rules differ:
 // * the lister and the diff of tick k are queued before member(k - 1)'s successors know whether that member kernel
@@ -45,6 +47,15 @@
 //   so every launch of a later tick returns at once, member(k) before its resets, and the host goes on from
 //   lister(kw + 1) with the mode off. A member that writes usually takes a gossip slot in the same launch: then
 //   hg == hw and the gossip halt's path is taken (the host queues the front of kw + 1 again after the gossip plane).
+//
+// * a recorded watch sample of tick t (watch.hip, swimhip_watch_series.h) is a reader only: it is queued directly
+//   behind member(t - 1) (row shards: behind k_unpack_a(t - 1)) and in front of the front of t, and describes the state
+//   at rest at tick t, which exists once member(t - 1) and, where one is needed, the gossip plane of t - 1 have run.
+//   hg <= t: member(t - 1) took a slot (hg = t; the gossip plane of t - 1 has not run) or an earlier halt kept it from
+//   running; hd != 0: a lister of tick <= t - 1 stopped the batch in front of member(t - 1) (hd <= t: no lister of a later
+//   tick has run yet); lister-free, hw <= t - 1: an earlier member kernel wrote and member(t - 1) returned at once, while
+//   hw == t is member(t - 1) itself, which is complete. The engine has one stream: nothing runs beside the sample, so
+//   the words it reads were stored by earlier launches only. The host queues a void sample again where it resumes.
 //
 // The raises: raise_gossip_halt (a member taking a slot, tick_reset), raise_gate_halt (k_unpack_a's gate),
 // raise_diff_halt and count_listed (the lister), note_wrote (member control). The host clears a word after it has
@@ -95,6 +106,12 @@ __device__ __forceinline__ bool halted_before(const uint32_t* halt, uint32_t k) 
 __device__ __forceinline__ bool halted_uncommitted(const uint32_t* halt, uint32_t k) { return halted_before(halt, k + 1u); }
 __device__ __forceinline__ bool halted_member(const uint32_t* halt, uint32_t k, bool lf = false) {
   return halted_before(halt, k) || *(volatile const uint32_t*)(halt + HALT_DIFF) != 0u || halted_wrote(halt, k, lf);
+}
+
+// a recorded watch sample of tick t >= 1, queued behind member(t - 1): the state at rest at tick t does not exist (yet)
+__device__ __forceinline__ bool halted_sample(const uint32_t* halt, uint32_t t, bool lf) {
+  return halted_uncommitted(halt, t - 1u) || *(volatile const uint32_t*)(halt + HALT_DIFF) != 0u ||
+         halted_wrote(halt, t - 1u, lf);
 }
 
 __device__ __forceinline__ void raise_gossip_halt(uint32_t* halt, uint32_t k) {

@@ -86,6 +86,8 @@ int spec_batch(swim_handle* h, Step& s) {
     // (the first tick's front may have been queued with the tick before it: then its lister ran)
     const uint32_t mlf = !lf ? 0u : MT_LF | (kj >= k0 && !te ? MT_NOLIST : 0u);
     launch_member(d, kj, h->stream, te, true, false, mlf);
+    int wr;
+    if ((wr = watch_tick_done(h, kj + 1u, true, lf)) != SWIM_OK) return wr;  // void if member(kj) halts or returned at once
     s.need_front = j + 1 == nb;
     if (!s.need_front) front(kj + 1, j + 1);
   }
@@ -163,6 +165,8 @@ int spec_batch(swim_handle* h, Step& s) {
     if ((gr = grow_caps(h)) != SWIM_OK) return gr;
   }
   launch_gossip(d, kh, h->stream, events_of(h, kh, ih));
+  int wr;
+  if ((wr = watch_tick_done(h, kh + 1u, false, false)) != SWIM_OK) return wr;  // (the in-batch sample of kh + 1 was void)
   h->gossip_idle = false;
   h->gossip_ran = true;
   s.need_front = true;  // the front of kh + 1 returned at once
@@ -210,6 +214,8 @@ int tick_one_gpu(swim_handle* h, Step& s) {
     int xr;
     if ((xr = held_allreduce(h)) != SWIM_OK) return xr;
   }
+  int wr;
+  if ((wr = watch_tick_done(h, k + 1u, false, false)) != SWIM_OK) return wr;  // (diff(k + 1), if queued, writes no row)
   h->tick++;
   ++s.i;
   return SWIM_OK;
@@ -242,6 +248,7 @@ int shard_spec_batch(swim_handle* h, Step& s) {
     launch_tick_a(d, kj, h->stream, tj, true);
     if ((xr = exchange_inline(h, d.xa_recv, d.XA_PEER, d.xa_scnt, d.xa_rcnt, true)) != SWIM_OK) return xr;
     launch_tick_b(d, kj, h->stream, tj, false, true);
+    if ((xr = watch_tick_done(h, kj + 1u, true, false)) != SWIM_OK) return xr;  // void from the gate's halt of kj on
   }
   HIPCK(hipMemcpyAsync((void*)(h->hflag + HF_SHARD_HALT), &d.halt[HALT_GOSSIP], 4, hipMemcpyDeviceToHost, h->stream));
   HIPCK(hipStreamSynchronize(h->stream));
@@ -257,6 +264,7 @@ int shard_spec_batch(swim_handle* h, Step& s) {
   const uint32_t ih = i + (kh - k);
   if ((xr = exchange_rest(h, d.xa_send, d.xa_recv, d.XA_PEER)) != SWIM_OK) return xr;
   if ((xr = shard_tick_rest(h, kh, events_of(h, kh, ih))) != SWIM_OK) return xr;
+  if ((xr = watch_tick_done(h, kh + 1u, false, false)) != SWIM_OK) return xr;
   h->tick = kh + 1ull;
   s.i = ih + 1;
   return SWIM_OK;
@@ -271,6 +279,7 @@ int shard_tick(swim_handle* h, Step& s) {
   launch_tick_a(d, k, h->stream, te);
   if ((xr = exchange(h, d.xa_send, d.xa_recv, d.XA_PEER, d.xa_scnt, d.xa_rcnt, true)) != SWIM_OK) return xr;
   if ((xr = shard_tick_rest(h, k, te)) != SWIM_OK) return xr;
+  if ((xr = watch_tick_done(h, k + 1u, false, false)) != SWIM_OK) return xr;
   h->tick++;
   ++s.i;
   return SWIM_OK;
@@ -310,6 +319,7 @@ extern "C" int swim_step(swim_handle* h, uint32_t n) {
   if (h->tick + n >= (1ull << 28)) return SWIM_ECAPACITY;  // deadlines are stored in 29 bits
   int rc;
   if ((rc = prof_prepare(h, n)) != SWIM_OK) return rc;
+  if (!h->recording.empty()) watch_record_prune(h);
   const uint64_t first = h->tick;
   const Dev& d = h->d;
   const bool no_batch = d.churn || h->no_spec || (h->cfg.flags & SWIM_FLAG_PROFILE_ALL);  // (PROFILE_ALL times every tick's gossip plane)

@@ -11,10 +11,15 @@
 // order of arrival. The smallest key is kept as the largest complement, so one memset of zeros prepares a sample.
 // Stamps are [3][K][N] words: the lanes of a wave touch consecutive words, read only where the predicate holds and
 // written only on the NEVER -> tick change, so a steady cluster stores nothing. Nothing of the engine's state is written.
+//
+// A recorded sample (swimhip_watch_series.h) is the same launch queued by step.hip behind a tick (watch_record_tick):
+// its tallies go to that tick's entry of the series instead of the watch's own block, `now` is the tick it describes,
+// and inside a speculative batch it reads the halt words first and returns at once when that state does not exist yet
+// (spec.h halted_sample). A sample that ran leaves tick + 1 in its entry's first spare word.
 #include <algorithm>
 #include <cstring>
 
-#include "../../include/swimhip_watch.h"
+#include "../../include/swimhip_watch_series.h"
 #include "dev_util.h"
 #include "group.h"
 
@@ -26,8 +31,9 @@ namespace {
 constexpr uint32_t WATCH_ROWS = SWIM_WATCH_BLOCK_ROWS, WATCH_K = SWIM_WATCH_MAX_SUBJECTS;
 constexpr uint32_t WATCH_NEVER = SWIM_WATCH_NEVER;
 // the tallies, on the device and in LDS: [K] ABSENT, [K] SUSPECT, [K] DEAD, [K] ~key_min, [K] key_max, then the rows
-// counted (and three words of padding)
+// counted, then (a series entry) tick + 1 of the sample that filled it, and two words of padding
 constexpr uint32_t T_AB = 0, T_SU = 1, T_DE = 2, T_MN = 3, T_MX = 4, T_PLANES = 5;
+constexpr uint32_t T_NOBS = 0, T_MARK = 1, T_TAIL = 4;  // the words after the planes
 
 struct WatchIn {
   const uint32_t* rowk;
@@ -40,6 +46,10 @@ struct WatchIn {
   uint32_t* tally;       // [T_PLANES K + 4], zero
   uint32_t* stamps;      // [3 or 2][K][N] or null
   uint32_t N, NS, NS8, NL, lo, now, K;
+  // a recorded sample: rec != 0 (tally is the series entry of tick now); queued inside a speculative batch: halt is
+  // Dev::halt (lf: of a lister-free batch), else null
+  const uint32_t* halt;
+  uint32_t rec, lf;
 };
 
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) { return ~wave_min(~v); }
@@ -50,6 +60,8 @@ __device__ __forceinline__ void stamp(uint32_t* p, uint32_t now) {
 template <bool K8>
 __global__ __launch_bounds__(WATCH_ROWS) void k_watch(const WatchIn in) {
   __shared__ uint32_t acc[T_PLANES * WATCH_K], nobs;
+  // (kernel arguments and halt words: the whole grid decides alike, before the first barrier)
+  if (in.halt && halted_sample(in.halt, in.now, in.lf != 0u)) return;
   const uint32_t t = threadIdx.x, lane = t & 63u, K = in.K, N = in.N;
   for (uint32_t i = t; i < T_PLANES * K; i += WATCH_ROWS) acc[i] = 0;
   if (t == 0) nobs = 0;
@@ -121,7 +133,8 @@ __global__ __launch_bounds__(WATCH_ROWS) void k_watch(const WatchIn in) {
     else
       atomicMax(&in.tally[i], v);
   }
-  if (t == 0 && nobs) atomicAdd(&in.tally[T_PLANES * K], nobs);
+  if (t == 0 && nobs) atomicAdd(&in.tally[T_PLANES * K + T_NOBS], nobs);
+  if (in.rec && t == 0 && blockIdx.x == 0) in.tally[T_PLANES * K + T_MARK] = in.now + 1u;
 }
 
 }  // namespace
@@ -138,6 +151,13 @@ struct swim_watch {
   size_t o_subj = 0, o_slot = 0, o_inc = 0, o_sel = 0, o_stamps = 0, tally_words = 0;
   std::vector<uint32_t> host;  // the tallies as copied back
   swim_watch* owner = nullptr;  // a part's group watch
+  // the recording (swimhip_watch_series.h): entry i of the series, tally_words each, is the sample of tick
+  // rec_t0 + i rec_every. rec_on: samples are still queued (on the handle's recording list); after a stop rec_n entries
+  // are complete. A group watch keeps the parameters, its parts the series.
+  uint32_t* series = nullptr;
+  uint32_t rec_every = 0, rec_cap = 0, rec_n = 0;
+  uint64_t rec_t0 = 0;
+  bool rec_on = false;
 };
 
 namespace {
@@ -153,6 +173,8 @@ size_t up64(size_t x) { return (x + 63) & ~(size_t)63; }
 void unregister(swim_watch* w) {
   auto& v = w->h->watches;
   v.erase(std::remove(v.begin(), v.end(), w), v.end());
+  auto& r = w->h->recording;
+  r.erase(std::remove(r.begin(), r.end(), w), r.end());
 }
 
 // frees w and its parts; the parts leave their shards' lists
@@ -165,6 +187,7 @@ void watch_free(swim_watch* w) {
   if (w->dev) {
     hipSetDevice((int)w->h->cfg.device);
     hipFree(w->dev);
+    if (w->series) hipFree(w->series);
   }
   delete w;
 }
@@ -181,7 +204,7 @@ int create_one(swim_handle* h, const uint32_t* subjects, uint32_t k, const uint3
   w->has_inc = inc_target != nullptr;
   w->has_sel = observers != nullptr;
   if (inc_target) w->inc.assign(inc_target, inc_target + k);
-  w->tally_words = T_PLANES * (size_t)k + 4;
+  w->tally_words = T_PLANES * (size_t)k + T_TAIL;
   w->host.assign(w->tally_words, 0u);
   // sorted by subject, remembering the caller's index
   std::vector<uint32_t> ord(k), tab(3 * (size_t)k, 0u);
@@ -220,13 +243,10 @@ int create_one(swim_handle* h, const uint32_t* subjects, uint32_t k, const uint3
   return SWIM_OK;
 }
 
-// one shard's sample: one memset, one kernel, one copy back
-int sample_one(swim_watch* w, Tallies* o) {
+// k_watch of tick `now` into `tally` (zero), queued on the handle's stream; halt: see WatchIn
+int launch_watch(swim_watch* w, uint32_t* tally, uint32_t now, bool rec, const uint32_t* halt, bool lf) {
   swim_handle* h = w->h;
   const Dev& d = h->d;
-  const uint32_t K = w->K;
-  static_assert(SWIM_WATCH_MAX_SUBJECTS <= 256 && T_PLANES * 4 <= 24, "the copy back is at most 24 K + 16 bytes");
-  hipSetDevice((int)h->cfg.device);
   WatchIn in{};
   in.rowk = d.rowk;
   in.rowk8 = d.rowk8;
@@ -235,24 +255,25 @@ int sample_one(swim_watch* w, Tallies* o) {
   in.subj = (const uint32_t*)(w->dev + w->o_subj);
   in.slot = (const uint32_t*)(w->dev + w->o_slot);
   in.inc = w->has_inc ? (const uint32_t*)(w->dev + w->o_inc) : nullptr;
-  in.tally = (uint32_t*)w->dev;
+  in.tally = tally;
   in.stamps = (w->flags & SWIM_WATCH_STAMPS) ? (uint32_t*)(w->dev + w->o_stamps) : nullptr;
-  in.N = d.N, in.NS = d.NS, in.NS8 = d.NS8, in.NL = d.NL, in.lo = d.lo, in.now = (uint32_t)h->tick, in.K = K;
-  HIPCK(hipMemsetAsync(w->dev, 0, 4 * w->tally_words, h->stream));
+  in.N = d.N, in.NS = d.NS, in.NS8 = d.NS8, in.NL = d.NL, in.lo = d.lo, in.now = now, in.K = w->K;
+  in.halt = halt, in.rec = rec ? 1u : 0u, in.lf = lf ? 1u : 0u;
   const uint32_t grid = cdiv(d.NL, WATCH_ROWS);
   if (d.rowk8)
     k_watch<true><<<grid, WATCH_ROWS, 0, h->stream>>>(in);
   else
     k_watch<false><<<grid, WATCH_ROWS, 0, h->stream>>>(in);
   HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(w->host.data(), w->dev, 4 * w->tally_words, hipMemcpyDeviceToHost, h->stream));
-  const int rc = check_err(h);  // (waits for the stream)
-  if (rc != SWIM_OK) return rc;
-  const uint32_t* t = w->host.data();
-  const uint32_t rows = t[T_PLANES * K];
-  o->tick = h->tick;
+  return SWIM_OK;
+}
+
+// a tally block as copied back -> what a sample reports
+void decode(const swim_watch* w, const uint32_t* t, uint64_t tick, Tallies* o) {
+  const uint32_t K = w->K, rows = t[T_PLANES * K + T_NOBS];
+  o->tick = tick;
   o->n_observers = rows;
-  o->path = d.rowk8 ? SWIM_CENSUS_PATH_KEY8 : SWIM_CENSUS_PATH_KEY32;
+  o->path = w->h->d.rowk8 ? SWIM_CENSUS_PATH_KEY8 : SWIM_CENSUS_PATH_KEY32;
   o->counts.resize(4 * (size_t)K);
   o->mn.resize(K);
   o->mx.resize(K);
@@ -264,26 +285,49 @@ int sample_one(swim_watch* w, Tallies* o) {
     o->mn[j] = ~t[T_MN * K + j];
     o->mx[j] = t[T_MX * K + j];
   }
+}
+
+// one shard's sample: one memset, one kernel, one copy back
+int sample_one(swim_watch* w, Tallies* o) {
+  swim_handle* h = w->h;
+  static_assert(SWIM_WATCH_MAX_SUBJECTS <= 256 && T_PLANES * 4 <= 24, "the copy back is at most 24 K + 16 bytes");
+  static_assert(T_MARK < T_TAIL, "the mark is one of the words after the planes");
+  hipSetDevice((int)h->cfg.device);
+  HIPCK(hipMemsetAsync(w->dev, 0, 4 * w->tally_words, h->stream));
+  int rc = launch_watch(w, (uint32_t*)w->dev, (uint32_t)h->tick, false, nullptr, false);
+  if (rc != SWIM_OK) return rc;
+  HIPCK(hipMemcpyAsync(w->host.data(), w->dev, 4 * w->tally_words, hipMemcpyDeviceToHost, h->stream));
+  rc = check_err(h);  // (waits for the stream)
+  if (rc != SWIM_OK) return rc;
+  decode(w, w->host.data(), h->tick, o);
   return SWIM_OK;
+}
+
+// o (zeroed by combine_begin) widened by one shard's partial p: counts add, key ranges widen
+void combine_begin(uint32_t K, Tallies* o) {
+  o->counts.assign(4 * (size_t)K, 0u);
+  o->mn.assign(K, 0xFFFFFFFFu);
+  o->mx.assign(K, 0u);
+  o->n_observers = 0;
+}
+void combine_add(uint32_t K, Tallies* o, const Tallies& p) {
+  for (size_t i = 0; i < o->counts.size(); ++i) o->counts[i] += p.counts[i];
+  for (uint32_t j = 0; j < K; ++j) o->mn[j] = std::min(o->mn[j], p.mn[j]), o->mx[j] = std::max(o->mx[j], p.mx[j]);
+  o->n_observers += p.n_observers;
+  o->tick = p.tick;
+  o->path = p.path;
 }
 
 int sample_any(swim_watch* w, Tallies* o) {
   if (w->parts.empty()) return sample_one(w, o);
   // the shards' partial samples combined as the census's: counts add, key ranges widen
   const uint32_t K = w->K;
-  o->counts.assign(4 * (size_t)K, 0u);
-  o->mn.assign(K, 0xFFFFFFFFu);
-  o->mx.assign(K, 0u);
-  o->n_observers = 0;
+  combine_begin(K, o);
   Tallies p;
   for (size_t r = 0; r < w->parts.size(); ++r) {
     const int rc = sample_one(w->parts[r], &p);
     if (rc != SWIM_OK) return fail(w->h, rc, "shard " + std::to_string(r) + ": " + w->parts[r]->h->err);
-    for (size_t i = 0; i < o->counts.size(); ++i) o->counts[i] += p.counts[i];
-    for (uint32_t j = 0; j < K; ++j) o->mn[j] = std::min(o->mn[j], p.mn[j]), o->mx[j] = std::max(o->mx[j], p.mx[j]);
-    o->n_observers += p.n_observers;
-    o->tick = p.tick;
-    o->path = p.path;
+    combine_add(K, o, p);
   }
   return SWIM_OK;
 }
@@ -298,10 +342,112 @@ void fill(struct swim_watch_sample* out, const Tallies& t) {
   if (out->key_max) std::copy(t.mx.begin(), t.mx.end(), out->key_max);
 }
 
+// ---- the recording ----
+
+// entries complete so far: the samples of the ticks <= the handle's tick (a stopped recording: as many as it had)
+uint32_t recorded(const swim_watch* w) {
+  if (!w->rec_on) return w->rec_n;
+  const swim_watch* p = w->parts.empty() ? w : w->parts[0];
+  const uint64_t n = (p->h->tick - w->rec_t0) / w->rec_every + 1;
+  return (uint32_t)std::min<uint64_t>(n, w->rec_cap);
+}
+bool armed(const swim_watch* w) { return w->rec_on && recorded(w) < w->rec_cap; }
+
+void record_off(swim_watch* w) {
+  w->rec_n = recorded(w);
+  w->rec_on = false;
+  for (swim_watch* p : w->parts) record_off(p);
+  auto& r = w->h->recording;
+  r.erase(std::remove(r.begin(), r.end(), w), r.end());
+}
+
+// one shard: the series allocated and zeroed, the sample of t0 taken and waited for
+int record_one(swim_watch* w, uint32_t every, uint32_t cap) {
+  swim_handle* h = w->h;
+  hipSetDevice((int)h->cfg.device);
+  if (w->rec_on) record_off(w);
+  if (w->series) {
+    HIPCK(hipStreamSynchronize(h->stream));
+    HIPCK(hipFree(w->series));
+    w->series = nullptr;
+  }
+  const size_t bytes = 4 * w->tally_words * (size_t)cap;
+  if (hipMalloc(&w->series, bytes) != hipSuccess) {
+    w->series = nullptr;
+    return fail(h, SWIM_ENOMEM, "swim_watch_record: hipMalloc of " + std::to_string(bytes) + " B failed");
+  }
+  HIPCK(hipMemsetAsync(w->series, 0, bytes, h->stream));
+  w->rec_every = every, w->rec_cap = cap, w->rec_n = 0, w->rec_t0 = h->tick, w->rec_on = true;
+  h->recording.push_back(w);
+  // the sample of t0: this watch's alone (another armed watch took its sample of this tick when the tick came to rest,
+  // before whatever host call may have followed it)
+  int rc = launch_watch(w, w->series, (uint32_t)h->tick, true, nullptr, false);
+  if (rc == SWIM_OK) rc = check_err(h);  // (waits for the stream)
+  if (rc != SWIM_OK) record_off(w);
+  return rc;
+}
+
+// entries [first, first + n) of one shard's series, decoded; the stream has been waited for
+int series_one(swim_watch* w, uint32_t first, uint32_t n, std::vector<Tallies>* out) {
+  swim_handle* h = w->h;
+  hipSetDevice((int)h->cfg.device);
+  const size_t tw = w->tally_words;
+  std::vector<uint32_t> buf(tw * n);
+  const int rc = check_err(h);  // (waits for the stream)
+  if (rc != SWIM_OK) return rc;
+  if (n) HIPCK(hipMemcpy(buf.data(), w->series + tw * first, 4 * tw * n, hipMemcpyDeviceToHost));
+  out->resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t tick = w->rec_t0 + (uint64_t)(first + i) * w->rec_every;
+    const uint32_t* t = &buf[tw * i];
+    if (t[T_PLANES * w->K + T_MARK] != (uint32_t)tick + 1u)
+      return fail(h, SWIM_EDEVICE, "swim_watch_series: the sample of tick " + std::to_string(tick) + " did not run (entry " +
+                                       std::to_string(first + i) + " holds mark " + std::to_string(t[T_PLANES * w->K + T_MARK]) + ")");
+    decode(w, t, tick, &(*out)[i]);
+  }
+  return SWIM_OK;
+}
+
+int series_any(swim_watch* w, uint32_t first, uint32_t n, std::vector<Tallies>* out) {
+  if (w->parts.empty()) return series_one(w, first, n, out);
+  out->assign(n, Tallies());
+  for (Tallies& t : *out) combine_begin(w->K, &t);
+  std::vector<Tallies> part;
+  for (size_t r = 0; r < w->parts.size(); ++r) {
+    const int rc = series_one(w->parts[r], first, n, &part);
+    if (rc != SWIM_OK) return fail(w->h, rc, "shard " + std::to_string(r) + ": " + w->parts[r]->h->err);
+    for (uint32_t i = 0; i < n; ++i) combine_add(w->K, &(*out)[i], part[i]);
+  }
+  return SWIM_OK;
+}
+
 }  // namespace
 
 namespace swim {
+// step.hip, where tick t comes to rest: the armed recordings' samples of t (handle.h watch_tick_done)
+int watch_record_tick(swim_handle* h, uint32_t t, bool in_batch, bool lf) {
+  for (swim_watch* w : h->recording) {
+    if (t < w->rec_t0 || (t - w->rec_t0) % w->rec_every) continue;
+    const uint64_t idx = (t - w->rec_t0) / w->rec_every;
+    if (idx >= w->rec_cap) continue;  // the series fills up in this call (it leaves the list at the next one's start)
+    uint32_t* entry = w->series + w->tally_words * idx;
+    // the series was zeroed when it was armed, and a void launch stores nothing; outside a batch the entry is zeroed
+    // again all the same, so that the host's own launch can never add to an earlier one
+    if (!in_batch) HIPCK(hipMemsetAsync(entry, 0, 4 * w->tally_words, h->stream));
+    const int rc = launch_watch(w, entry, t, true, in_batch ? h->d.halt : nullptr, lf);
+    if (rc != SWIM_OK) return rc;
+  }
+  return SWIM_OK;
+}
+
+// swim_step's start: a series that is full (its last entry's tick is behind the handle's) leaves the list
+void watch_record_prune(swim_handle* h) {
+  auto& r = h->recording;
+  r.erase(std::remove_if(r.begin(), r.end(), [](swim_watch* w) { return !armed(w); }), r.end());
+}
+
 void watch_free_all(swim_handle* h) {
+  h->recording.clear();
   while (!h->watches.empty()) {
     swim_watch* w = h->watches.back();
     h->watches.pop_back();
@@ -438,6 +584,87 @@ int swim_run_until(swim_handle* h, swim_watch* w, uint32_t cond, uint32_t max_ti
     }
     const uint32_t n = std::min(check_every, max_ticks - done);
     rc = swim_step(h, n);
+    if (rc != SWIM_OK) return rc;
+    done += n;
+  }
+}
+
+int swim_watch_record(swim_watch* w, uint32_t every, uint32_t cap) {
+  if (!w || w->owner || every == 0 || cap == 0) return SWIM_EINVAL;
+  if ((uint64_t)cap * (T_PLANES * (uint64_t)w->K + T_TAIL) > SWIM_WATCH_SERIES_MAX_WORDS || armed(w)) return SWIM_EINVAL;
+  if (w->parts.empty()) return record_one(w, every, cap);
+  if (w->rec_on) record_off(w);
+  for (size_t r = 0; r < w->parts.size(); ++r) {
+    const int rc = record_one(w->parts[r], every, cap);
+    if (rc != SWIM_OK) {
+      for (swim_watch* p : w->parts) record_off(p);
+      return fail(w->h, rc, "shard " + std::to_string(r) + ": " + w->parts[r]->h->err);
+    }
+  }
+  w->rec_every = every, w->rec_cap = cap, w->rec_n = 0, w->rec_t0 = w->parts[0]->rec_t0, w->rec_on = true;
+  return SWIM_OK;
+}
+
+int swim_watch_record_stop(swim_watch* w) {
+  if (!w || w->owner || w->rec_cap == 0) return SWIM_EINVAL;
+  if (w->rec_on) record_off(w);
+  return SWIM_OK;
+}
+
+int swim_watch_series(swim_watch* w, uint32_t first, uint32_t n, uint64_t* ticks, uint64_t* n_observers,
+                      uint32_t* counts, uint32_t* key_min, uint32_t* key_max, uint32_t* n_recorded) {
+  if (!w || w->rec_cap == 0) return SWIM_EINVAL;
+  const uint32_t have = recorded(w), K = w->K;
+  if (n_recorded) *n_recorded = have;
+  if ((uint64_t)first + n > have) return SWIM_EINVAL;
+  std::vector<Tallies> es;
+  const int rc = series_any(w, first, n, &es);
+  if (rc != SWIM_OK) return rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    const Tallies& t = es[i];
+    if (ticks) ticks[i] = t.tick;
+    if (n_observers) n_observers[i] = t.n_observers;
+    if (counts) std::copy(t.counts.begin(), t.counts.end(), counts + 4 * (size_t)K * i);
+    if (key_min) std::copy(t.mn.begin(), t.mn.end(), key_min + (size_t)K * i);
+    if (key_max) std::copy(t.mx.begin(), t.mx.end(), key_max + (size_t)K * i);
+  }
+  return SWIM_OK;
+}
+
+int swim_run_until_recorded(swim_handle* h, swim_watch* w, uint32_t cond, uint32_t max_ticks, uint32_t chunk,
+                            uint64_t* met_tick, uint32_t* met, uint32_t* ticks_run) {
+  if (!h || !w || !met_tick || !met || !ticks_run || w->h != h || chunk == 0 || cond > SWIM_UNTIL_INC_GE) return SWIM_EINVAL;
+  if (cond == SWIM_UNTIL_INC_GE && !w->has_inc) return SWIM_EINVAL;
+  if (!h->grp && h->d.W > 1)
+    return fail(h, SWIM_EUNSUPPORTED, "swim_run_until_recorded on one shard: the verdict needs every shard's tallies");
+  if (!armed(w)) return SWIM_EINVAL;
+  *met_tick = 0;
+  *met = 0;
+  *ticks_run = 0;
+  const uint64_t start = h->tick;
+  // the first entry of a tick >= start
+  uint32_t next = (uint32_t)((start - w->rec_t0 + w->rec_every - 1) / w->rec_every);
+  std::vector<Tallies> es;
+  for (uint32_t done = 0;;) {
+    const uint32_t have = recorded(w);
+    if (have > next) {
+      int rc = series_any(w, next, have - next, &es);
+      if (rc != SWIM_OK) return rc;
+      for (const Tallies& t : es)
+        if (swim_watch_met(cond, w->K, t.counts.data(), t.mn.data(), t.mx.data(), w->has_inc ? w->inc.data() : nullptr) == 1) {
+          *met_tick = t.tick;
+          *met = 1;
+          *ticks_run = done;
+          return SWIM_OK;
+        }
+      next = have;
+    }
+    if (done == max_ticks || next >= w->rec_cap) {
+      *ticks_run = done;
+      return SWIM_OK;
+    }
+    const uint32_t n = std::min(chunk, max_ticks - done);
+    const int rc = swim_step(h, n);
     if (rc != SWIM_OK) return rc;
     done += n;
   }

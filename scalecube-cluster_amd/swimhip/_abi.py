@@ -246,9 +246,20 @@ WATCH_SIGNATURES = {
 }
 
 
+# include/swimhip_watch_series.h (recording on a watch: a per-tick series taken inside swim_step)
+WATCH_SERIES_MAX_WORDS = 1 << 26
+_U64P = C.POINTER(C.c_uint64)
+WATCH_SERIES_SIGNATURES = {
+    "swim_watch_record": (C.c_int, [_W, C.c_uint32, C.c_uint32]),
+    "swim_watch_record_stop": (C.c_int, [_W]),
+    "swim_watch_series": (C.c_int, [_W, C.c_uint32, C.c_uint32, _U64P, _U64P, _U32P, _U32P, _U32P, _U32P]),
+    "swim_run_until_recorded": (C.c_int, [_H, _W, C.c_uint32, C.c_uint32, C.c_uint32, _U64P, _U32P, _U32P]),
+}
+
+
 def bind_watch(lib):
-    """Attach the watch entry points (engine library only)."""
-    for name, (res, args) in WATCH_SIGNATURES.items():
+    """Attach the watch entry points, the recording's included (engine library only)."""
+    for name, (res, args) in {**WATCH_SIGNATURES, **WATCH_SERIES_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -274,6 +274,12 @@ class SimulatedCluster:
         ok, ticks, _ = watch.run_until(self._h, cond, max_ticks, check_every)
         return ok, ticks
 
+    def run_until_recorded(self, watch, cond, max_ticks, chunk=64):
+        """Like run_until with check_every = 1, at the batches' speed: `watch` has a recording armed (Watch.record), the
+        cluster steps `chunk` ticks per call and the recorded entries are looked at after each:
+        (met, met_tick, ticks_run), met_tick exact to the recording's `every`, ticks_run overshooting by less than chunk."""
+        return watch.run_until_recorded(self._h, cond, max_ticks, chunk)
+
     def counters(self):
         c = _abi.SwimCounters()
         self._ck(self.lib.swim_counters_get(self._h, C.byref(c)), "swim_counters_get")

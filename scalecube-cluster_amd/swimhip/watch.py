@@ -24,6 +24,24 @@ class WatchSample:
     path: int             # _abi.CENSUS_PATH_KEY8 / KEY32
 
 
+@dataclass
+class WatchSeries:
+    """Entries of a recording (include/swimhip_watch_series.h): entry i is the sample of tick ticks[i]."""
+    ticks: np.ndarray        # (n,) uint64
+    n_observers: np.ndarray  # (n,) uint64
+    counts: np.ndarray       # (n, K, 4) uint32
+    key_min: np.ndarray      # (n, K) uint32
+    key_max: np.ndarray      # (n, K) uint32
+    n_recorded: int = 0      # entries complete when it was read (the whole series, not only the range read)
+
+    def __len__(self):
+        return len(self.ticks)
+
+    def entry(self, i, path=0) -> WatchSample:
+        return WatchSample(tick=int(self.ticks[i]), n_observers=int(self.n_observers[i]), counts=self.counts[i],
+                           key_min=self.key_min[i], key_max=self.key_max[i], path=path)
+
+
 def met(cond, counts, key_min, key_max, inc_target=None) -> bool:
     """Whether condition `cond` (_abi.UNTIL_*) holds for every watched subject: swim_watch_met in numpy."""
     counts = np.asarray(counts).reshape(-1, 4)
@@ -51,6 +69,25 @@ def combine(parts: Sequence[WatchSample]) -> WatchSample:
                        counts=np.sum([p.counts for p in parts], axis=0, dtype=np.uint32),
                        key_min=np.minimum.reduce([p.key_min for p in parts]),
                        key_max=np.maximum.reduce([p.key_max for p in parts]), path=p0.path)
+
+
+def combine_series(parts: Sequence[WatchSeries]) -> WatchSeries:
+    """The whole cluster's series from its row shards' partial ones: combine, entry by entry."""
+    p0 = parts[0]
+    assert all(np.array_equal(p.ticks, p0.ticks) for p in parts), "partial series of different ticks"
+    return WatchSeries(ticks=p0.ticks.copy(), n_observers=np.sum([p.n_observers for p in parts], axis=0, dtype=np.uint64),
+                       counts=np.sum([p.counts for p in parts], axis=0, dtype=np.uint32),
+                       key_min=np.minimum.reduce([p.key_min for p in parts]),
+                       key_max=np.maximum.reduce([p.key_max for p in parts]),
+                       n_recorded=min(p.n_recorded for p in parts))
+
+
+def first_met(series: WatchSeries, cond, inc_target=None) -> Optional[int]:
+    """The index of the first entry of `series` that meets `cond` (_abi.UNTIL_*), or None: a host scan with met."""
+    for i in range(len(series)):
+        if met(cond, series.counts[i], series.key_min[i], series.key_max[i], inc_target):
+            return i
+    return None
 
 
 def combine_stamps(parts: Sequence[Dict[str, np.ndarray]]) -> Dict[str, np.ndarray]:
@@ -129,6 +166,52 @@ class Watch:
                                             C.byref(s)), "swim_run_until")
         return bool(ok.value), int(ticks.value), self._sample_of(s, arrs)
 
+    def record(self, every=1, cap=4096):
+        """Arm recording (swim_watch_record): from the current tick on the engine samples every `every`-th tick inside
+        step(), speculative batches included, into a device series of `cap` entries."""
+        self._check(self.lib.swim_watch_record(self._w, every, cap), "swim_watch_record")
+
+    def stop(self):
+        """swim_watch_record_stop: the series stays readable."""
+        self._check(self.lib.swim_watch_record_stop(self._w), "swim_watch_record_stop")
+
+    def recorded(self) -> int:
+        """Entries complete so far."""
+        n = C.c_uint32()
+        self._check(self.lib.swim_watch_series(self._w, 0, 0, None, None, None, None, None, C.byref(n)),
+                    "swim_watch_series")
+        return int(n.value)
+
+    def series(self, first=0, n=None) -> WatchSeries:
+        """Entries [first, first + n) of the recording (n = None: every complete entry from `first` on; none if `first`
+        is past them). A stated range that reaches past the complete entries is refused (SWIM_EINVAL)."""
+        have = self.recorded()
+        if n is None:
+            n = max(have - first, 0)
+            first = min(first, have)
+        ticks, nobs = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        counts, mn, mx = np.zeros((n, self.k, 4), np.uint32), np.zeros((n, self.k), np.uint32), \
+            np.zeros((n, self.k), np.uint32)
+        p64 = C.POINTER(C.c_uint64)
+        got = C.c_uint32()
+        self._check(self.lib.swim_watch_series(self._w, first, n, ticks.ctypes.data_as(p64), nobs.ctypes.data_as(p64),
+                                               counts.ctypes.data_as(_P), mn.ctypes.data_as(_P), mx.ctypes.data_as(_P),
+                                               C.byref(got)), "swim_watch_series")
+        return WatchSeries(ticks, nobs, counts, mn, mx, int(got.value))
+
+    def first_met(self, cond, first=0):
+        """(tick, index) of the first recorded entry from `first` on that meets `cond`, or None."""
+        s = self.series(first)
+        i = first_met(s, cond, self.inc_target)
+        return None if i is None else (int(s.ticks[i]), first + i)
+
+    def run_until_recorded(self, handle, cond, max_ticks, chunk=64):
+        """swim_run_until_recorded on the watch's handle: (met, met_tick, ticks_run)."""
+        tick, ok, ran = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.swim_run_until_recorded(handle, self._w, cond, max_ticks, chunk, C.byref(tick),
+                                                     C.byref(ok), C.byref(ran)), "swim_run_until_recorded")
+        return bool(ok.value), int(tick.value), int(ran.value)
+
     def close(self):
         if self._w:
             self.lib.swim_watch_destroy(self._w)
@@ -146,7 +229,9 @@ class Watch:
 
 
 class GroupWatch:
-    """One watch per shard of a ThreadShardGroup, combined in Python as the n_gpus handle combines them in C."""
+    """One watch per shard of a ThreadShardGroup, combined in Python as the n_gpus handle combines them in C. A
+    recording is one series per shard, combined on read (combine_series); there is no run_until_recorded here (one
+    shard cannot give the verdict, swim_run_until_recorded refuses it): step the group and look at first_met()."""
 
     def __init__(self, parts: Sequence[Watch]):
         self.parts = list(parts)
@@ -161,6 +246,22 @@ class GroupWatch:
 
     def met(self, cond, sample: Optional[WatchSample] = None) -> bool:
         return self.parts[0].met(cond, sample or self.sample())
+
+    def record(self, every=1, cap=4096):
+        for p in self.parts:
+            p.record(every, cap)
+
+    def stop(self):
+        for p in self.parts:
+            p.stop()
+
+    def series(self, first=0, n=None) -> WatchSeries:
+        return combine_series([p.series(first, n) for p in self.parts])
+
+    def first_met(self, cond, first=0):
+        s = self.series(first)
+        i = first_met(s, cond, self.inc_target)
+        return None if i is None else (int(s.ticks[i]), first + i)
 
     def close(self):
         for p in self.parts:
