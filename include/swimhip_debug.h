@@ -126,6 +126,17 @@ int swim_debug_diff_dirty(swim_handle* h, uint64_t* out, size_t n);
 #define SWIM_LT_ON 12u            /* 1: the next member kernel takes the light path, 0: it does not */
 int swim_debug_light(swim_handle* h, uint64_t* out, size_t n);
 
+/* The light path while nobody is dead ("Round 13"). The engine keeps one device word, first_dead, that
+ * is at most every member's dead tick (a kill, a completed leave and dormant members lower it; nothing raises it). A
+ * member kernel launched for a tick below it skips the light path's dead-member lookups (the ping target's, a hop
+ * target's, the SYNC and SYNC_ACK destinations'): every one of them would answer "alive".
+ * swim_debug_light_sure: n <= 3 entries; the counter since create, counted under swim_debug_light's conditions;
+ * entry 2 (n > 2) costs a readback of every member's dead tick. A multi-device or sharded handle: SWIM_EUNSUPPORTED. */
+#define SWIM_LS_SKIPPED 0u     /* member-ticks finished by the light path with the dead lookups skipped */
+#define SWIM_LS_FIRST_DEAD 1u  /* the word now (0xFFFFFFFF: nobody ever died, left or was dormant) */
+#define SWIM_LS_MIN_DEAD 2u    /* the minimum over the members' dead ticks now: never below the word */
+int swim_debug_light_sure(swim_handle* h, uint64_t* out, size_t n);
+
 /* the masks' invariant, tested directly: the number of (row, chunk) pairs marked clean whose keys differ from the
  * baseline's chunk, which on one GPU is what the first row marked clean in that chunk holds: all clean rows must agree
  * (0 in a correct engine). One pass over the key plane. */

@@ -229,8 +229,7 @@ int swim_sync(swim_handle* h) {
 int swim_kill(swim_handle* h, uint32_t m) {
   GROUP_ALL(swim_kill(s, m));
   if (!h || m >= h->d.N) return SWIM_EINVAL;
-  uint32_t t = (uint32_t)h->tick;
-  HIPCK(hipMemcpyAsync(h->d.dead_tick + m, &t, 4, hipMemcpyHostToDevice, h->stream));
+  launch_kill(h->d, m, (uint32_t)h->tick, h->stream);  // dead_tick[m], and its lower bound first_dead
   // (the crashed member's holder state stays as it is: it never sends again, sends to it fail, and its slots expire)
   return check_err(h);
 }

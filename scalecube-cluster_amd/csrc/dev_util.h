@@ -455,7 +455,15 @@ __device__ __forceinline__ uint32_t suspicion_ticks(const Dev& d, uint32_t size,
 // from tick k + 1
 __device__ __forceinline__ void on_sweep(const Dev& d, uint32_t g, uint32_t m, uint32_t k) {
   if ((uint32_t)(d.slot_gid[g] >> 32) != m || d.slot_subj[g] != m || rec_status(d.slot_key[g]) != ST_DEAD) return;
+  if (uint32_t* fd = first_dead_word(d)) atomicMin(fd, k + 1u);  // the lower bound of dead_tick (engine.h), lowered on the device
   d.dead_tick[m] = k + 1u;
+}
+
+// first_dead as a kernel reads it: no member is dead at tick k while k < first_dead_at(d). A Dev without the word
+// (built by hand) reads as 0: nothing is known.
+__device__ __forceinline__ uint32_t first_dead_at(const Dev& d) {
+  const uint32_t* fd = first_dead_word(d);
+  return fd ? *fd : 0u;
 }
 
 // S entries: creation tick + 1 (0 = never held), SWEPT, REBORN

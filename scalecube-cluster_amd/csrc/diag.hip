@@ -203,6 +203,31 @@ extern "C" int swim_debug_light(swim_handle* h, uint64_t* out, size_t n) {
   return SWIM_OK;
 }
 
+// test surface (swim_debug_light_sure): the light path's dead-lookup counter (member_light.h LS_SKIP: the word behind
+// swim_debug_light's in every counter row), the first_dead word, and the minimum of dead_tick it must not exceed
+static_assert(SH_LIGHT + SWIM_LT_ON == SH_LIGHT_SURE, "swim_debug_light's entries end where swim_debug_light_sure's begin");
+extern "C" int swim_debug_light_sure(swim_handle* h, uint64_t* out, size_t n) {
+  if (!h || !out || n > SWIM_LS_MIN_DEAD + 1) return SWIM_EINVAL;
+  if (h->grp || h->d.W > 1 || h->d.XW > 1) return SWIM_EUNSUPPORTED;
+  const Dev& d = h->d;
+  HIPCK(hipStreamSynchronize(h->stream));
+  std::vector<unsigned long long> sh((size_t)CSH * CSTRIDE);
+  HIPCK(hipMemcpy(sh.data(), d.ctr_sh, 8 * sh.size(), hipMemcpyDeviceToHost));
+  uint64_t v[SWIM_LS_MIN_DEAD + 1] = {};
+  for (uint32_t r = 0; r < CSH; ++r)
+    for (uint32_t i = 0; i < SWIM_LS_FIRST_DEAD; ++i) v[i] += sh[(size_t)r * CSTRIDE + SH_LIGHT_SURE + i];
+  uint32_t fd = 0;  // (no word: nothing is known, as first_dead_at reads it)
+  if (const uint32_t* w = first_dead_word(d)) HIPCK(hipMemcpy(&fd, w, 4, hipMemcpyDeviceToHost));
+  v[SWIM_LS_FIRST_DEAD] = fd;
+  if (n > SWIM_LS_MIN_DEAD) {
+    std::vector<uint32_t> dt(d.N);
+    HIPCK(hipMemcpy(dt.data(), d.dead_tick, 4ull * d.N, hipMemcpyDeviceToHost));
+    v[SWIM_LS_MIN_DEAD] = *std::min_element(dt.begin(), dt.end());
+  }
+  for (size_t i = 0; i < n; ++i) out[i] = v[i];
+  return SWIM_OK;
+}
+
 namespace swim {
 
 // test surface (swim_debug_holders): per member of [first, first + n): its gossip count, the receipt-ring positions of

@@ -99,8 +99,12 @@ constexpr uint32_t CSH = 64, CSTRIDE = 64;  // Dev::ctr_sh rows, 512 B apart
 // (member.hip, lf_count): messages resolved, narrow messages decided without a stream, of those pinned; the host adds
 // them to C_ACKRES_ALL, to C_DIFFMSG_ALL and C_DMSGSKIP, and to the pinned count (api.hip lf_counts).
 // Every row's words SH_LIGHT .. SH_LIGHT + LT_N - 1 (a 128-B line of their own): what the member kernel's light path did
-// and what fell back to the general body (member_light.h LT_*; swim_debug_light sums the rows).
-constexpr uint32_t SH_LF = 8, SH_HALT = 16, SH_PINDEC = 32, SH_LIGHT = 48;
+// and what fell back to the general body (member_light.h LT_*; swim_debug_light sums the rows); the word behind them:
+// the member-ticks whose dead lookups it skipped (LS_SKIP; swim_debug_light_sure).
+// Row 0's word SH_FIRST_DEAD, on the pinned count's line (no atomic reaches that line while a member kernel runs): the
+// lower bound of dead_tick (first_dead_word, its low 32 bits).
+constexpr uint32_t SH_LF = 8, SH_HALT = 16, SH_PINDEC = 32, SH_FIRST_DEAD = 33, SH_LIGHT = 48;
+constexpr uint32_t SH_LIGHT_SURE = 60;  // the first word behind the LT_ counters (asserted where LT_N and SWIM_LT_ON are known)
 enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29,
            // dirty-chunk skipping of the SYNC diff (one GPU): narrow 2048-subject chunks the lister had
            // streamed, their subjects over the timed and over all launches (2 B each in swim_counters.diff_key_bytes*),
@@ -199,6 +203,8 @@ struct Dev {
 
   // ---- network / fault history (NetworkEmulator settings per epoch) ----
   uint32_t* dead_tick;  // [N] tick from which the member is dead, NEVER = alive
+  // first_dead, a lower bound of every dead_tick entry at all times, is a spare word of the counter rows
+  // (first_dead_word below; no field here: the struct's size is part of the pinned device footprint)
   // the epoch table and the link count are held in Dev itself: a kernel reads them with scalar loads at the tick's
   // (uniform) epoch, not as a chain of dependent vector loads in every send (xmit_ep)
   uint32_t ep_from[MAX_EPOCHS];   // first tick of each settings epoch (NEVER = unused)
@@ -564,6 +570,16 @@ void launch_user_gossips(const Dev& d, uint32_t k, const uint64_t* q, uint32_t n
 void launch_churn(const Dev& d, uint32_t k, void* stream);
 void launch_md_column(const Dev& d, uint32_t m, uint32_t u, void* stream);
 void launch_join(const Dev& d, uint32_t m, uint32_t k, const uint32_t* seeds, uint32_t n, void* stream);  // RUMOR mode, at ticks k % ping_t == 0
+void launch_kill(const Dev& d, uint32_t m, uint32_t t, void* stream);
+
+// "first_dead": one word that is at most every dead_tick entry, at all times, so that k < first_dead means no member
+// is dead at tick k (the light path then skips its dead_tick lookups, member_light.h). Every writer of dead_tick
+// lowers it first or with the write (k_init_members, swim_kill, on_sweep); it never goes up again (k_join leaves it:
+// conservative, never wrong). It lives in row 0 of the counter rows (SH_FIRST_DEAD, its low 32 bits); a Dev built by
+// hand without counter rows has none, which reads as 0 (first_dead_at, dev_util.h)
+__host__ __device__ __forceinline__ uint32_t* first_dead_word(const Dev& d) {
+  return d.ctr_sh ? (uint32_t*)(d.ctr_sh + SH_FIRST_DEAD) : nullptr;
+}
 void launch_hash(const Dev& d, uint64_t* out, uint32_t now, void* stream);
 void launch_held_add(const Dev& d, const int32_t* sum, void* stream);
 void launch_s_scrub(const Dev& d, uint32_t now, void* stream);  // every SCRUB ticks: stale S entries cleared

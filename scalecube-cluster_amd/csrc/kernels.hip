@@ -50,6 +50,7 @@ __global__ void k_init_members(Dev d) {
   d.log_pos[m] = 0;
   d.spchg[m] = 0;
   d.dead_tick[m] = dormant ? 0u : NEVER;  // a process not started yet refuses connections, like a dead one
+  if (m == 0) *first_dead_word(d) = d.n_dormant ? 0u : NEVER;  // the lower bound of the entries above (engine.h)
   d.md_version[m] = 0;
   d.rc_cnt[m] = 0;
   d.rc_off[m] = 0;
@@ -308,7 +309,7 @@ struct JoinSeeds {
 };
 __global__ void k_join(Dev d, uint32_t m, uint32_t k, JoinSeeds js, uint32_t n) {
   if (threadIdx.x != 0) return;
-  d.dead_tick[m] = NEVER;
+  d.dead_tick[m] = NEVER;  // (first_dead stays: a lower bound only ever goes down)
   d.start_tick[m] = k;
   d.nextPing[m] = k + mc_ping_t(d, m);
   d.nextGossip[m] = d.firstGossip[m] = k + d.gossip_t;
@@ -320,6 +321,17 @@ void launch_join(const Dev& d, uint32_t m, uint32_t k, const uint32_t* seeds, ui
   JoinSeeds js{};
   for (uint32_t i = 0; i < n && i < 16; ++i) js.s[i] = seeds[i];
   hipLaunchKernelGGL(k_join, dim3(1), dim3(64), 0, (hipStream_t)stream, d, m, k, js, n);
+}
+
+// swim_kill: member m is dead from tick t; the lower bound of dead_tick first (engine.h first_dead_word)
+__global__ void k_kill(Dev d, uint32_t m, uint32_t t) {
+  if (threadIdx.x != 0) return;
+  atomicMin(first_dead_word(d), t);
+  d.dead_tick[m] = t;
+}
+
+void launch_kill(const Dev& d, uint32_t m, uint32_t t, void* stream) {
+  hipLaunchKernelGGL(k_kill, dim3(1), dim3(64), 0, (hipStream_t)stream, d, m, t);
 }
 
 void launch_hash(const Dev& d, uint64_t* out, uint32_t now, void* stream) {

@@ -4,11 +4,16 @@
 //
 // member_tick_body reaches each of these cases through phases that load what they need when they get there, often
 // behind the lane's own stores. Here the lane loads in rounds of independent loads (round 1: every address that follows
-// from m, k and the triage; round 2: what those values name; round 3: the ping target's dead_tick), decides in
+// from m, k and the triage; round 2: what those values name; round 3, only while some member may be dead: the ping
+// target's dead_tick), decides in
 // registers whether the tick is one of the cases below, and only then commits: until the decision nothing is stored
 // and no atomic is issued, so a lane that finds anything else runs member_tick_body from scratch (the fallback and
 // the reference: SWIM_NO_LIGHT=1 runs every member through it). What is committed is what the general body would have
 // left in memory, word for word: only the words that change are stored.
+//
+// While no member has ever died, left or been dormant (k < first_dead, one launch-uniform word: engine.h) every dead_tick
+// lookup answers "alive": the hop's, the warming loads, round 3 and send_sync's own are skipped, so a ping is two
+// rounds and a commit. Once the word stops holding, the path is the one described above.
 //
 // Who comes here (member_triage, lc): a live member whose only causes this tick are an inbound SYNC list, a due
 // request event (next_evt), a due ping, a due periodic SYNC or an empty gossip round; no routed receipts, host
@@ -44,6 +49,15 @@ enum : uint32_t {
   LT_N
 };
 constexpr uint32_t lt_bit(uint32_t i) { return 1u << i; }
+// beside them, the counter of swim_debug_light_sure: word SH_LIGHT_SURE. A light attempt returns it as a bit above
+// the LT_ bits
+enum : uint32_t {
+  LS_SKIP = 0,  // member-ticks finished by the light path without a dead_tick lookup (nobody dead: first_dead)
+  LS_N
+};
+constexpr uint32_t LS_SKIP_BIT = 1u << 16;
+static_assert(SH_LIGHT + LT_N == SH_LIGHT_SURE && SH_LIGHT_SURE + LS_N <= CSTRIDE && LT_N <= 16,
+              "the light path's words fit its line of the counter row");
 constexpr uint32_t LT_FALLBACK = ((1u << LT_N) - 1u) & ~((1u << LT_FB_RESHUFFLE) - 1u);
 
 // the launch takes the light path: never with link delays (a delayed message is stored, redelivered and ordered by
@@ -108,6 +122,7 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
   const uint32_t selc = sy ? *selp : 0u;
   const uint32_t ping_t = pg ? mc_ping_t(d, m) : 0u, timeout_t = pg ? mc_timeout_t(d, m) : 0u;
   const int ep = epoch_at(d, k);
+  const uint32_t fdead = first_dead_at(d);  // (one word, the same for every lane)
 
   const uint32_t tsize = w0.x, fdLen = w0.y, nsub = w3.x, npath = w3.y, nfetch = w3.z, fnext = w3.w;
   if (ep < 0) return lt_bit(LT_FB_OTHER);
@@ -128,10 +143,15 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
     if (pingIdx >= (int32_t)fdLen) return lt_bit(LT_FB_RESHUFFLE);
   }
 
-  // ---- round 2: what those values name (the two sends' destinations are only warmed: send_sync loads them)
+  // Nobody is dead at k while k < first_dead (engine.h): every "is x dead at k" below is answered without its load.
+  const bool alive_all = k < fdead;
+  const int dd = alive_all ? 0 : -1;  // xmit_ep's: the destination is known alive, or looked up
+
+  // ---- round 2: what those values name (while some member may be dead, the two sends' destinations are only warmed
+  // below: send_sync loads them; with alive_all it is told they are alive and loads nothing)
   const bool hit = arr && nsub == 1 && s0.x == p0.x;  // the pending subscription takes the PING_ACK
   const uint32_t tgt = pg ? d.fdl[li * d.LCAP + (uint32_t)pingIdx] : 0u;
-  const uint32_t hop_dt = hop ? d.dead_tick[p0.w] : NEVER;
+  const uint32_t hop_dt = hop && !alive_all ? d.dead_tick[p0.w] : NEVER;
   const uint32_t ack_st = hit ? d.rowk[li * d.NS + s0.z] & 3u : ST_ALIVE;
   uint32_t starget = 0;
   if (sy) {
@@ -145,12 +165,15 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
     light_msg_load(d, pb, mb);
     if (d.m_next[(size_t)pb * d.MSGCAP + mb.i] != NEVER) return lt_bit(LT_FB_PAYLOADS);
   }
-  uint32_t warm = 0;
-  if (p1 && ma.sync()) warm += d.dead_tick[ma.src];
-  if (sy) warm += d.dead_tick[starget];
-  asm volatile("" ::"v"(warm));  // keep the warming loads
-  // ---- round 3
-  const uint32_t tgt_dt = pg ? d.dead_tick[tgt] : NEVER;
+  uint32_t tgt_dt = NEVER;
+  if (!alive_all) {
+    uint32_t warm = 0;
+    if (p1 && ma.sync()) warm += d.dead_tick[ma.src];
+    if (sy) warm += d.dead_tick[starget];
+    asm volatile("" ::"v"(warm));  // keep the warming loads
+    // ---- round 3
+    if (pg) tgt_dt = d.dead_tick[tgt];
+  }
 
   if (two) {
     const uint32_t why = light_msg_check(d, m, mb);
@@ -161,7 +184,7 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
   if (pg && light_xmit(d, ep, K_PING, m, tgt, k, m, cid, k >= tgt_dt) < 0) return lt_bit(LT_FB_SEND);
 
   // ---- commit: the general body's phases in their order, on the words they change
-  uint32_t did = lt_bit(LT_TICKS);
+  uint32_t did = lt_bit(LT_TICKS) | (alive_all ? LS_SKIP_BIT : 0u);
   ML L;  // the fields send_sync and link_flush read
   L.d = &d, L.m = m, L.k = k, L.ep = ep, L.tsize = tsize, L.syncSeq = w1.w, L.pend = NEVER, L.ntl = 0, L.spec = spec;
   L.lk_i = NEVER, L.lk_o = NEVER;
@@ -179,7 +202,7 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
       const LightMsg& q = (r == 0) == swap ? mb : ma;
       L.c[C_R] += q.psize;
       L.c[C_SYNCMERGE]++;
-      if (q.sync()) send_sync(L, K_SYNC_ACK, q.src, q.ciss, q.ccnt, !(q.kind & (KF_ABS | KF_LATE)));
+      if (q.sync()) send_sync(L, K_SYNC_ACK, q.src, q.ciss, q.ccnt, !(q.kind & (KF_ABS | KF_LATE)), dd);
     }
   }
   uint32_t nsub2 = nsub, npath2 = npath, pmin = NEVER, smin = NEVER;
@@ -227,7 +250,7 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
     did |= lt_bit(LT_SYNC);
     d.nextSync[m] = ns + d.sync_t;
     *selp = selc + 1u;
-    send_sync(L, K_SYNC, starget, NONE32, 0);
+    send_sync(L, K_SYNC, starget, NONE32, 0, false, dd);
   }
   link_flush(L);
   if (L.syncSeq != w1.w) ms->syncSeq = L.syncSeq;
@@ -248,6 +271,8 @@ __device__ __forceinline__ void light_count(const Dev& d, uint32_t bits, uint32_
     const uint32_t v = (uint32_t)__popcll(__ballot((bits >> i) & 1u));
     if (lane == 0 && v) atomicAdd(&cs[i], (unsigned long long)v);
   }
+  const uint32_t skip = (uint32_t)__popcll(__ballot(bits & LS_SKIP_BIT));
+  if (lane == 0 && skip) atomicAdd(&cs[SH_LIGHT_SURE - SH_LIGHT + LS_SKIP], (unsigned long long)skip);
 }
 
 // the general body's member-ticks of a wave (LT_GENERAL)

@@ -233,12 +233,13 @@ __device__ __forceinline__ void link_flush(ML& L) {
 
 // prepareSyncDataMsg (MembershipProtocolImpl.java:446-454) + transport.send; false if the send failed
 // res: a SYNC_ACK sent in the tick its SYNC was merged (k_ack_resolve may derive its diff from the write logs)
+// dd: xmit_ep's (whether dst is dead at k, when the caller knows; -1: looked up)
 __device__ __forceinline__ bool send_sync(ML& L, uint32_t kind, uint32_t dst, uint32_t ciss, uint32_t ccnt,
-                                          bool res = false) {
+                                          bool res = false, int dd = -1) {
   const Dev& d = *L.d;
   uint32_t seq = L.syncSeq++;
   L.c[C_M]++;
-  const int e = xmit_ep(d, L.ep, kind, L.m, dst, L.k, L.m, seq);
+  const int e = xmit_ep(d, L.ep, kind, L.m, dst, L.k, L.m, seq, dd);
   if (e < 0) {
     L.c[C_LOST]++;
     return false;

@@ -299,6 +299,7 @@ DEBUG_SIGNATURES = {
     "swim_debug_diff_dirty": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
     "swim_debug_dirty_check": (C.c_int, [_H, C.POINTER(C.c_uint64)]),
     "swim_debug_light": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
+    "swim_debug_light_sure": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_size_t]),
     "swim_debug_prim_eval": (C.c_int, [C.c_uint32, _U32P, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_uint32]),
     "swim_debug_receipts_set": (C.c_int, [_H, _U32P, C.c_size_t, _U32P, C.c_size_t, C.c_uint32]),
@@ -434,6 +435,23 @@ def debug_light(lib, handle):
     if rc != 0:
         raise RuntimeError(f"swim_debug_light rc={rc}")
     return dict(zip(LIGHT_NAMES, (int(x) for x in out)))
+
+
+# swim_debug_light_sure's entries (include/swimhip_debug.h SWIM_LS_*)
+LIGHT_SURE_NAMES = ["skipped", "first_dead", "min_dead"]
+
+
+def debug_light_sure(lib, handle):
+    """{name: value} of the light path while nobody is dead: member-ticks with the dead lookups skipped, the
+    first_dead word and the minimum of the members' dead ticks
+    (include/swimhip_debug.h swim_debug_light_sure)."""
+    fn = lib.swim_debug_light_sure
+    fn.restype, fn.argtypes = DEBUG_SIGNATURES["swim_debug_light_sure"]
+    out = (C.c_uint64 * len(LIGHT_SURE_NAMES))()
+    rc = fn(handle, out, len(LIGHT_SURE_NAMES))
+    if rc != 0:
+        raise RuntimeError(f"swim_debug_light_sure rc={rc}")
+    return dict(zip(LIGHT_SURE_NAMES, (int(x) for x in out)))
 
 
 def debug_dirty_check(lib, handle):
