@@ -72,6 +72,34 @@ int push_epoch(swim_handle* h) {
   return SWIM_OK;
 }
 
+// the host readers' walk of a message buffer (msg_slots.h msg_for_each): the overflow count, the shards' counters, then
+// the two regions' slots in use, ascending. slots (optional): the slot of each message returned.
+int msgs_read(swim_handle* h, uint32_t b, std::vector<SyncMsg>& out, std::vector<uint32_t>* slots_out) {
+  const Dev& d = h->d;
+  out.clear();
+  uint32_t nover = 0;
+  HIPCK(hipMemcpy(&nover, d.nmsg + b, 4, hipMemcpyDeviceToHost));
+  const MsgLayout L = msg_layout(d.MSGCAP, d.msh);
+  uint32_t cnt[MSG_SHARDS_MAX] = {0};
+  if (L.S > 1) {
+    std::vector<unsigned long long> sh((size_t)(L.S + 1) * CSTRIDE);
+    HIPCK(hipMemcpy(sh.data(), d.ctr_sh, 8 * sh.size(), hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < L.S; ++s) cnt[s] = (uint32_t)sh[(size_t)(s + 1) * CSTRIDE + MSG_CTR_WORD + b];
+  }
+  std::vector<uint32_t> slots;
+  msg_for_each(L, cnt, nover, [&](uint32_t i) { slots.push_back(i); });
+  if (slots_out) *slots_out = slots;
+  if (slots.empty()) return SWIM_OK;
+  // (ascending: the fast region's slots lie in [0, first overflow slot), the overflow region's are contiguous)
+  const uint32_t nf = (uint32_t)(std::lower_bound(slots.begin(), slots.end(), L.R) - slots.begin());
+  std::vector<SyncMsg> fast(nf ? slots[nf - 1] + 1 : 0), over(slots.size() - nf);
+  if (!fast.empty()) HIPCK(hipMemcpy(fast.data(), d.msgs[b], fast.size() * sizeof(SyncMsg), hipMemcpyDeviceToHost));
+  if (!over.empty()) HIPCK(hipMemcpy(over.data(), d.msgs[b] + L.R, over.size() * sizeof(SyncMsg), hipMemcpyDeviceToHost));
+  for (uint32_t q = 0; q < nf; ++q) out.push_back(fast[slots[q]]);
+  out.insert(out.end(), over.begin(), over.end());
+  return SWIM_OK;
+}
+
 }  // namespace swim
 
 namespace {
@@ -940,11 +968,8 @@ int swim_debug_set_incarnation(swim_handle* h, uint32_t m, uint32_t inc) {
   HIPCK(hipStreamSynchronize(h->stream));
   if (h->tick > 0) {  // a SYNC / SYNC_ACK of m still in flight carries m's live row: the host write would reach it
     const uint32_t b = (uint32_t)((h->tick - 1) & 1);
-    uint32_t nm = 0;
-    HIPCK(hipMemcpy(&nm, d.nmsg + b, 4, hipMemcpyDeviceToHost));
-    nm = std::min(nm, d.MSGCAP);
-    std::vector<SyncMsg> v(nm);
-    if (nm) HIPCK(hipMemcpy(v.data(), d.msgs[b], nm * sizeof(SyncMsg), hipMemcpyDeviceToHost));
+    std::vector<SyncMsg> v;
+    if (const int rc = msgs_read(h, b, v)) return rc;
     for (const SyncMsg& q : v)
       if (q.src == m && q.payload == NEVER && !(q.kind & KF_DEFER)) {
         h->err = "swim_debug_set_incarnation: member " + std::to_string(m) + " has a live-row payload in flight";
@@ -1008,6 +1033,25 @@ int swimdbg_send_log(swim_handle* h, uint32_t* out, size_t cap, size_t* n) {
   cnt = (uint32_t)std::min<size_t>(cnt, cap);
   HIPCK(hipMemcpy(out, h->d.dbg_send, 20ull * cnt, hipMemcpyDeviceToHost));
   *n = cnt;
+  return SWIM_OK;
+}
+
+// debugging aid (not part of the ABI header): the message buffer of the latest tick as the host readers walk it
+// (msgs_read). out[0] shards (Dev::msh), out[1] Q, out[2] R, out[3] messages in fast slots, out[4] in overflow slots,
+// out[5] the highest slot in use (~0: none), out[6] 1 if every message read from its slot names a member as its sender
+int swimdbg_msg_slots(swim_handle* h, uint64_t* out) {
+  if (!h || !out || h->grp || h->d.W > 1 || h->d.XW > 1 || h->d.implicit || h->tick == 0) return SWIM_EINVAL;
+  HIPCK(hipStreamSynchronize(h->stream));
+  const Dev& d = h->d;
+  const MsgLayout L = msg_layout(d.MSGCAP, d.msh);
+  std::vector<SyncMsg> v;
+  std::vector<uint32_t> slots;
+  if (const int rc = msgs_read(h, (uint32_t)((h->tick - 1) & 1), v, &slots)) return rc;
+  uint64_t nfast = 0, ok = 1;
+  for (uint32_t i : slots) nfast += i < L.R;
+  for (const SyncMsg& q : v) ok &= q.src < d.N && q.dst < d.N;
+  out[0] = L.S, out[1] = L.Q, out[2] = L.R, out[3] = nfast, out[4] = slots.size() - nfast;
+  out[5] = slots.empty() ? ~0ull : slots.back(), out[6] = ok;
   return SWIM_OK;
 }
 

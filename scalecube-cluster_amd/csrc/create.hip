@@ -280,6 +280,24 @@ static int fill_dev(swim_handle* h) {
     const char* nl = getenv("SWIM_NO_LIGHT");
     d.light = nl && strcmp(nl, "0") ? 0u : LIGHT_ON;
   }
+  // message-slot shards (msg_slots.h): the same handles from MSG_SHARD_MIN_N members on, except a cold join's (its seed
+  // answers every member's SYNC from one lane: one shard's demand, which the sharded buffer serves only up to about
+  // three quarters of MSGCAP). SWIM_MSG_SHARDS=n, a power of two from 1 to 32, overrides it on any one-GPU handle with
+  // stored tables, whatever its init mode: 1 is the tests' reference path and the A/B switch on one build.
+  // A value that is no such number is refused on every handle; on a row or slot shard and with implicit views a valid
+  // one is read and not used: those keep one counter.
+  d.msh = 1;
+  const bool one_gpu_stored = d.W == 1 && d.XW == 1 && !d.implicit;
+  if (one_gpu_stored && d.mode != SWIM_MODE_RUMOR && c.init_mode != SWIM_INIT_COLD_JOIN && d.N >= MSG_SHARD_MIN_N)
+    d.msh = MSG_SHARDS_MAX;
+  if (const char* e = getenv("SWIM_MSG_SHARDS")) {
+    const unsigned long v = strtoul(e, nullptr, 0);
+    if (v > MSG_SHARDS_MAX || !msg_shards_ok((uint32_t)v)) {
+      h->err = "SWIM_MSG_SHARDS must be a power of two from 1 to 32";
+      return SWIM_EINVAL;
+    }
+    if (one_gpu_stored) d.msh = (uint32_t)v;
+  }
   if (d.W > 1) {
     d.MW = kp.MW;
     d.NSCAP = 1u << 16;
@@ -373,7 +391,7 @@ static int alloc_table(swim_handle* h) {
     A(d.dq, (uint64_t)(d.EMAX + 2) * d.DQCAP) Z(d.dq_n, d.EMAX + 2) Z(d.dmark, N)
     A(d.ds_msg, d.DSCAP) A(d.ds_row, (uint64_t)d.DSCAP * d.NS) Z(d.ds_used, d.DSCAP) A(d.ds_free, d.DSCAP) A(d.ds_top, 1)
   }
-  if (d.exp & EXP_WAVE_CLOCK) A(d.wt, (uint64_t)(NL + 255) / 256 * 4 * 16)
+  if (d.exp & EXP_WAVE_CLOCK) Z(d.wt, (uint64_t)(NL + 255) / 256 * 4 * WT_WORDS)
   if (d.fastp4) {
     Z(d.evp_hash, N) Z(d.evp_n, N)
   }

@@ -161,13 +161,11 @@ int swim_debug_receipts_read(swim_handle* h, uint32_t first, uint32_t n, uint32_
     }
   }
   if (msg_out) {  // the tick's message buffer: arena rows taken, messages, and per sender those whose payload is a snapshot
-    uint32_t au = 0, nm = 0;
-    if ((rc = d2h(h, &au, d.arena_used + b, 4)) != SWIM_OK || (rc = d2h(h, &nm, d.nmsg + b, 4)) != SWIM_OK) return rc;
-    nm = std::min(nm, d.MSGCAP);
-    std::vector<SyncMsg> v(nm);
-    if ((rc = d2h(h, v.data(), d.msgs[b], nm * sizeof(SyncMsg))) != SWIM_OK) return rc;
+    uint32_t au = 0;
+    std::vector<SyncMsg> v;
+    if ((rc = d2h(h, &au, d.arena_used + b, 4)) != SWIM_OK || (rc = msgs_read(h, b, v)) != SWIM_OK) return rc;
     msg_out[0] = au;
-    msg_out[1] = nm;
+    msg_out[1] = (uint32_t)v.size();
     std::fill(msg_out + 2, msg_out + 2 + d.N, 0u);
     for (const SyncMsg& q : v)
       if (q.src < d.N && q.payload != NEVER && !(q.payload & PAY_RX)) msg_out[2 + q.src]++;

@@ -270,6 +270,57 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t* ctr) {
   return base + rank;
 }
 
+// ---- message slots (msg_slots.h): the device's side of the scheme ----
+// shard s's counter of buffer b: the low half of word MSG_CTR_WORD + b of counter row s + 1
+__device__ __forceinline__ uint32_t* msg_ctr(unsigned long long* ctr_sh, uint32_t s, uint32_t b) {
+  return (uint32_t*)(ctr_sh + (size_t)(s + 1u) * CSTRIDE + MSG_CTR_WORD + b);
+}
+// A slot of msgs[b] for each active lane that calls it together: one wave-aggregated returning add on the wave's shard
+// (its place in the grid), and for the lanes whose index reaches Q a second one on nmsg[b], among those lanes only.
+// Returns MSGCAP or more when no slot was left: the caller raises E_MSGS and stores nothing.
+__device__ __forceinline__ uint32_t msg_take(const Dev& d, uint32_t b) {
+  if (d.msh <= 1u) return wave_append(&d.nmsg[b]);
+  const MsgLayout L = msg_layout(d.MSGCAP, d.msh);
+  const uint32_t s = (blockIdx.x * 4u + (threadIdx.x >> 6)) & (L.S - 1u);
+  const uint32_t j = wave_append(msg_ctr(d.ctr_sh, s, b));
+  if (j < L.Q) return msg_fast_slot(L, s, j);
+  return msg_over_slot(L, wave_append(&d.nmsg[b]));
+}
+// the next buffer's shard counters back to zero, beside nmsg[nb] (one thread: tick_reset, tick_flag, tick_end)
+__device__ __forceinline__ void msg_reset(const Dev& d, uint32_t nb) {
+  for (uint32_t s = 0; d.msh > 1u && s < d.msh; ++s) *msg_ctr(d.ctr_sh, s, nb) = 0;
+}
+// The readers' walk of buffer b for a whole block (every thread calls it, blockDim >= MSG_SHARDS_MAX; one barrier when
+// sharded): the shards' fills into fill[] (LDS, [MSG_SHARDS_MAX]) and the enumeration. nover: nmsg[b].
+struct MsgWalk {
+  MsgLayout L;
+  MsgEnum E;
+};
+__device__ __forceinline__ MsgWalk msg_walk_block(unsigned long long* ctr_sh, uint32_t shards, uint32_t msgcap, uint32_t b,
+                                                  uint32_t nover, uint32_t* fill) {
+  MsgWalk w;
+  w.L = msg_layout(msgcap, shards);
+  uint32_t c_max = 0;
+  if (w.L.S > 1u) {  // (block-uniform)
+    if (threadIdx.x < w.L.S) fill[threadIdx.x] = msg_fill(w.L, *msg_ctr(ctr_sh, threadIdx.x, b));
+    __syncthreads();
+    for (uint32_t s = 0; s < w.L.S; ++s) c_max = max(c_max, fill[s]);
+    c_max = __builtin_amdgcn_readfirstlane(c_max);  // (block-uniform: the walk stays in scalar registers)
+  }
+  w.E = msg_enum(w.L, c_max, __builtin_amdgcn_readfirstlane(nover));
+  return w;
+}
+// position j's slot, NEVER for a hole (a fast slot its shard has not handed out): msg_slots.h's msg_pos_used and
+// msg_pos_slot on the walk's numbers. The one copy of it; k_sync_diff keeps the walk's fields in scalars of its own
+// (a MsgWalk held across its stream loop went to the stack) and calls it through the second form.
+__device__ __forceinline__ uint32_t msg_at(const MsgLayout& L, const MsgEnum& E, const uint32_t* fill, uint32_t j) {
+  if (j < E.nfast && !msg_pos_used(L, E, j, fill[msg_pos_shard(L, j)])) return NEVER;
+  return msg_pos_slot(L, E, j);
+}
+__device__ __forceinline__ uint32_t msg_at(const MsgWalk& w, const uint32_t* fill, uint32_t j) {
+  return msg_at(w.L, w.E, fill, j);
+}
+
 // the wave's sum (u32, and u64 as two 32-bit shuffles per step), minimum and maximum of a value every lane holds
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
@@ -304,6 +355,34 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
     if (lane >= o) v += u;
   }
   return v;
+}
+
+// The readers' dense walk for one wave, without LDS or a barrier (k_ack_resolve, a wave per message; every lane of the
+// wave calls both): lane s < S loads shard s's counter beside the overflow count, one round of loads, and keeps the
+// fills' inclusive prefix sum; total messages = the fills' sum + the overflow slots in use.
+// msg_at_wave: the q-th message's slot (msg_slots.h msg_dense_slot; q wave-uniform, below the total).
+struct MsgDense {
+  MsgLayout L;
+  uint32_t incl;         // this lane's shard: the fills' sum up to and with it (lanes >= S: the whole sum)
+  uint32_t nfast, total; // messages in fast slots, all messages
+};
+__device__ __forceinline__ MsgDense msg_walk_wave(unsigned long long* ctr_sh, uint32_t shards, uint32_t msgcap, uint32_t b,
+                                                  const uint32_t* nover_p, uint32_t lane) {
+  MsgDense w;
+  w.L = msg_layout(msgcap, shards);
+  uint32_t cnt = 0;
+  if (w.L.S > 1u && lane < w.L.S) cnt = *msg_ctr(ctr_sh, lane, b);
+  const uint32_t nover = __builtin_amdgcn_readfirstlane(*nover_p);
+  w.incl = w.L.S > 1u ? wave_incl_scan(msg_fill(w.L, cnt), lane) : 0u;
+  w.nfast = __builtin_amdgcn_readfirstlane(__shfl(w.incl, 63));
+  w.total = w.nfast + min(nover, w.L.cap - w.L.R);
+  return w;
+}
+__device__ __forceinline__ uint32_t msg_at_wave(const MsgDense& w, uint32_t q) {
+  if (q >= w.nfast) return w.L.R + (q - w.nfast);
+  const uint32_t s = (uint32_t)__popcll(__ballot(w.incl <= q));  // the shards wholly before q (lanes >= S: incl = nfast > q)
+  const uint32_t before = __shfl(w.incl, (int)(s ? s - 1u : 0u));  // (the fills' sum of the shards before s)
+  return msg_fast_slot(w.L, s, q - (s ? before : 0u));
 }
 
 // a member kernel's eight op counters (engine.h C_*) summed across the wave first, then one atomic each into the
@@ -556,6 +635,7 @@ __device__ __forceinline__ void tick_end(const Dev& d, uint32_t k) {
   if (t == 0) {
     uint32_t nb = (k + 1) & 1;
     d.nmsg[nb] = 0;
+    msg_reset(d, nb);
     d.arena_used[nb] = 0;
     *d.pool_used = 0;
     *d.rc_n = 0;
@@ -571,6 +651,7 @@ __device__ __forceinline__ void tick_end(const Dev& d, uint32_t k) {
 __device__ __forceinline__ void tick_reset(const Dev& d, uint32_t k) {
   const uint32_t nb = (k + 1) & 1;
   d.nmsg[nb] = 0;
+  msg_reset(d, nb);
   d.arena_used[nb] = 0;
   *d.pool_used = 0;
   if (d.ackres) *d.ndl = *d.ndlw = 0;
@@ -600,6 +681,7 @@ __device__ __forceinline__ void tick_flag(const Dev& d, uint32_t k) {
 #pragma unroll
   for (uint32_t i = 0; i < HSH_WORDS; ++i) sh[i] = d.hsh[i];
   d.nmsg[nb] = 0;
+  msg_reset(d, nb);
   d.arena_used[nb] = 0;
   *d.pool_used = 0;
   if (d.rfill) *d.rfill = 0;

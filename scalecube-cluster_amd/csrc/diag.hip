@@ -70,10 +70,12 @@ int exp_dump_member_cycles(swim_handle* h) {
 int exp_dump_wave_clock(swim_handle* h) {
   const Dev& d = h->d;
   const size_t nw = (size_t)(d.NL + 255) / 256 * 4;
-  std::vector<unsigned long long> w16(nw * 16), w(nw * 4);
-  HIPCK(hipMemcpy(w16.data(), d.wt, w16.size() * 8, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < nw; ++i)
+  std::vector<unsigned long long> w16(nw * 16), w(nw * 4), wall(nw * WT_WORDS);
+  HIPCK(hipMemcpy(wall.data(), d.wt, wall.size() * 8, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < nw; ++i) {
+    for (int j = 0; j < 16; ++j) w16[16 * i + j] = wall[WT_WORDS * i + j];
     for (int j = 0; j < 4; ++j) w[4 * i + j] = w16[16 * i + j];
+  }
   const unsigned long long M = (1ull << 48) - 1;
   unsigned long long t0 = ~0ull, tend = 0;
   for (size_t i = 0; i < nw; ++i) t0 = std::min(t0, w[4 * i]), tend = std::max(tend, w[4 * i + 3]);
@@ -88,6 +90,48 @@ int exp_dump_wave_clock(swim_handle* h) {
   }
   fprintf(stderr, "exp512: span %.2f us; mean per wave (us): start %.2f triage %.2f body %.2f cow %.2f\n",
           (tend - t0) / 100.0, sst / nw / 100.0, str / nw / 100.0, sbd / nw / 100.0, scw / nw / 100.0);
+  {  // send_sync's stamps (WT_SLOT0, WT_SLOT1, WT_LINK) of the waves that sent in this launch (a stamp outside the
+     // wave's bodies is an earlier launch's): the slot reservation's round trip and the time from its return to the
+     // list-link exchange's, per class; then the reservation's round trip against the order the waves issued it in
+    struct Snd {
+      unsigned long long at;
+      double res, lnk;
+      unsigned cls;
+    };
+    std::vector<Snd> snd;
+    for (size_t i = 0; i < nw; ++i) {
+      const unsigned long long a = wall[WT_WORDS * i + WT_SLOT0], b = wall[WT_WORDS * i + WT_SLOT1],
+                               c = wall[WT_WORDS * i + WT_LINK], lo = w[4 * i + 1] & M, hi = w[4 * i + 2];
+      if (a < lo || b < a || b > hi) continue;
+      snd.push_back({a, (b - a) / 100.0, c >= b && c <= hi ? (c - b) / 100.0 : -1.0, (unsigned)(w[4 * i + 1] >> 56)});
+    }
+    const auto quart = [](std::vector<double>& e, const char* what, int c) {
+      std::sort(e.begin(), e.end());
+      if (!e.empty())
+        fprintf(stderr, "exp512: class %d sending waves %zu %s us q1 %.2f med %.2f q3 %.2f max %.2f\n", c, e.size(), what,
+                e[e.size() / 4], e[e.size() / 2], e[3 * e.size() / 4], e.back());
+    };
+    for (int c = 0; c < 4; ++c) {
+      std::vector<double> res, lnk;
+      for (const Snd& s : snd)
+        if (s.cls == (1u << c)) {
+          res.push_back(s.res);
+          if (s.lnk >= 0) lnk.push_back(s.lnk);
+        }
+      quart(res, "slot reservation", c);
+      quart(lnk, "slot to link exchange", c);
+    }
+    std::sort(snd.begin(), snd.end(), [](const Snd& x, const Snd& y) { return x.at < y.at; });
+    const size_t G = 8;
+    for (size_t g = 0; g < G && snd.size() >= G; ++g) {  // eighths of the sending waves in issue order
+      const size_t i0 = g * snd.size() / G, i1 = (g + 1) * snd.size() / G;
+      std::vector<double> e;
+      for (size_t i = i0; i < i1; ++i) e.push_back(snd[i].res);
+      std::sort(e.begin(), e.end());
+      fprintf(stderr, "exp512: reservations %zu-%zu by issue order, issued %.2f-%.2f us: round trip med %.2f max %.2f\n", i0,
+              i1 - 1, (snd[i0].at - t0) / 100.0, (snd[i1 - 1].at - t0) / 100.0, e[e.size() / 2], e.back());
+    }
+  }
   for (size_t r = 0; r < 8 && r < nw; ++r) {
     const size_t i = ord[r];
     if (r == 0) {  // when the waves of each class finish their bodies (us from the kernel's first wave): quartiles

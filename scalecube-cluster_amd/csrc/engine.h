@@ -12,6 +12,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "msg_slots.h"
 #include "spec.h"
 #include "swim_common.h"
 
@@ -103,8 +104,13 @@ constexpr uint32_t CSH = 64, CSTRIDE = 64;  // Dev::ctr_sh rows, 512 B apart
 // the member-ticks whose dead lookups it skipped (LS_SKIP; swim_debug_light_sure).
 // Row 0's word SH_FIRST_DEAD, on the pinned count's line (no atomic reaches that line while a member kernel runs): the
 // lower bound of dead_tick (first_dead_word, its low 32 bits).
+// Rows 1 .. MSG_SHARDS_MAX, words MSG_CTR_WORD and MSG_CTR_WORD + 1 (their low halves; words 16-31 of these rows are a
+// 128-B line that nothing else touches): row s + 1 holds message-slot shard s's counters of the two message buffers
+// (msg_slots.h; Dev::msh shards). Never summed; zero at create, zeroed for the next buffer with nmsg (tick_reset).
 constexpr uint32_t SH_LF = 8, SH_HALT = 16, SH_PINDEC = 32, SH_FIRST_DEAD = 33, SH_LIGHT = 48;
 constexpr uint32_t SH_LIGHT_SURE = 60;  // the first word behind the LT_ counters (asserted where LT_N and SWIM_LT_ON are known)
+static_assert(MSG_SHARDS_MAX + 1 <= CSH && MSG_CTR_WORD >= SH_LF + 8 && MSG_CTR_WORD + 2 <= 32 && SH_LIGHT >= 32,
+              "the message-slot shards' counters have their line of rows 1 .. MSG_SHARDS_MAX to themselves");
 enum Ctr { C_R = 0, C_W, C_M, C_G, C_E, C_LOST, C_GCREATED, C_SYNCMERGE, C_DIFFMSG = 13, C_XU = 16, C_ACKRES = 24, C_ACKRES_ALL = 25, C_DIFFMSG_ALL = 26, C_DIFFWIDE = 27, C_DIFFWIDE_ALL = 28, C_NCTR = 29,
            // dirty-chunk skipping of the SYNC diff (one GPU): narrow 2048-subject chunks the lister had
            // streamed, their subjects over the timed and over all launches (2 B each in swim_counters.diff_key_bytes*),
@@ -150,6 +156,9 @@ constexpr uint32_t KF_RES = 0x400u;
 // is the message's payload (arena row or PAY_RX | rx index), NEVER for the live row, DESC_PIN | arena row for a pinned
 // live row, DESC_DEFER for a delayed message (sync_diff.hip desc_pay)
 constexpr uint32_t DESC_PIN = 0x80000000u, DESC_DEFER = 0xFFFFFFFEu;
+// without lists (no SYNC_ACK resolution) k_sync_diff walks the buffer's positions itself: a position whose slot holds
+// no message (msg_slots.h, a hole) is this entry, which stream_wide passes over
+constexpr uint32_t DESC_HOLE = 0xFFFFFFFDu;
 // On one GPU the narrow list holds one entry per item (four chunks of one message) with a chunk to stream, and the
 // fourth word is item index << 4 | the item's chunks to stream (k_ack_resolve; the others are known equal, Dev::rdirty)
 constexpr uint32_t NPER = 4;  // chunks per narrow item
@@ -337,8 +346,9 @@ struct Dev {
   uint32_t* hist_n;  // [1] W == 1: entries in use (grow_caps)
 
   // ---- SYNC messages (double-buffered by tick parity) ----
+  // slots handed out per shard (msg_slots.h, Dev::msh): msgs[b] is enumerated by msg_enum, not by a count
   SyncMsg* msgs[2];
-  uint32_t* nmsg;  // [2]
+  uint32_t* nmsg;  // [2] slots taken from the buffer's overflow region (msh == 1: every slot)
   uint32_t* arena[2];  // [ARENA_ROWS][NS] key-plane snapshots (a payload carries keys only)
   uint32_t* arena_used;  // [2]
   uint32_t* m_next; // [2][MSGCAP] next message of msgs[b] to the same destination
@@ -361,6 +371,9 @@ struct Dev {
   // that tick plus the candidates of the payloads it merged (first TL of them), their count (> TL: overflowed) and the
   // tick they belong to; the messages k_sync_diff streams this tick (the others are resolved)
   uint32_t ackres;    // 0: every payload streamed; ACKRES_ON, | ACKRES_DIRTY: k_ack_resolve consults rdirty (W == 1)
+  // message-slot shards of msgs[b] (msg_slots.h): a power of two, 1 (or 0, a Dev built by hand) = off. Beside ackres, in
+  // what was padding: the struct's size stays
+  uint32_t msh;
   uint32_t* tlog;     // [2][NL][TL]
   uint32_t* tl_n;     // [2][NL]
   uint32_t* tl_tick;  // [2][NL]
@@ -387,7 +400,7 @@ struct Dev {
   // host with ctr. ~1 400 waves adding to one word per tick serialise at its L2 channel (~13 ns each) and held every
   // later memory access of the waves still running (k_member_tick 44 -> 31 us at C3)
   unsigned long long* ctr_sh;  // [CSH][CSTRIDE]
-  unsigned long long* wt;   // SWIM_EXP & 512: per-wave timestamps of the latest k_member_tick [waves][16]
+  unsigned long long* wt;   // SWIM_EXP & 512: per-wave timestamps of the latest k_member_tick [waves][WT_WORDS]
   uint32_t* err;            // [8] bits, info...
   const Dev* self;          // device-resident copy of this struct (kernels index it through a pointer)
   uint32_t* hflag;          // host-mapped flag block, HF_BYTES (spec.h HFlag)

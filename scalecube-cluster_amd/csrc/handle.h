@@ -176,11 +176,15 @@ int exchange_rest(swim_handle* h, uint8_t* send, uint8_t* recv, uint64_t cap);
 int exchange(swim_handle* h, uint8_t* send, uint8_t* recv, uint64_t cap, unsigned long long* scnt,
              unsigned long long* rcnt, bool inline_packed);
 int held_allreduce(swim_handle* h);
+// api.hip: the messages of buffer b (one GPU, the stream idle), its slots in use in ascending slot order
+// (msg_slots.h); slots: each one's slot
+int msgs_read(swim_handle* h, uint32_t b, std::vector<SyncMsg>& out, std::vector<uint32_t>* slots = nullptr);
 // diag.hip
 int stats_dump(swim_handle* h, uint32_t k);
 int exp_dump_member_cycles(swim_handle* h);
 int exp_dump_wave_clock(swim_handle* h);
 int exp_dump_gossip_work(swim_handle* h);
+
 int prof_prepare(swim_handle* h, uint32_t n);
 bool prof_timed(const swim_handle* h, uint64_t tick);
 int prof_accumulate(swim_handle* h, uint64_t first, uint32_t n);

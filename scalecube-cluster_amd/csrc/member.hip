@@ -115,7 +115,7 @@ struct Lap {
       : d(dev), prof((dev.exp & EXP_CYCLES) != 0), tp(prof ? clock64() : 0) {}
   __device__ __forceinline__ void operator()(int slot) {
     if ((d.exp & EXP_WAVE_CLOCK) && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)__ballot(1)) - 1))
-      d.wt[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + 4 + slot] = wall_clock64();
+      d.wt[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * WT_WORDS + 4 + slot] = wall_clock64();
     if (!prof || slot > 4) return;  // (slots 5-10: finer wall-clock laps only)
     const unsigned long long t = clock64();
     if (d.exp & EXP_CYCLES_SUM)
@@ -725,7 +725,7 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   if (mt_spec_one_gpu(flag) && blockIdx.x == 0 && threadIdx.x == 0) tick_reset(d, k);
   // SWIM_EXP & 512 (timing experiment): wall clock of each wave at entry, after triage, after its bodies, at exit
   const bool wtime = (d.exp & EXP_WAVE_CLOCK) != 0;
-  unsigned long long* wt = wtime ? d.wt + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 : nullptr;
+  unsigned long long* wt = wtime ? d.wt + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * WT_WORDS : nullptr;
   if (wtime && (threadIdx.x & 63) == 0) wt[0] = wall_clock64();
   __shared__ uint32_t wc[4][4];  // [wave][class] busy members
   __shared__ uint32_t list[256];

@@ -202,7 +202,7 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
       const LightMsg& q = (r == 0) == swap ? mb : ma;
       L.c[C_R] += q.psize;
       L.c[C_SYNCMERGE]++;
-      if (q.sync()) send_sync(L, K_SYNC_ACK, q.src, q.ciss, q.ccnt, !(q.kind & (KF_ABS | KF_LATE)), dd);
+      if (q.sync()) send_sync<true>(L, K_SYNC_ACK, q.src, q.ciss, q.ccnt, !(q.kind & (KF_ABS | KF_LATE)), dd);
     }
   }
   uint32_t nsub2 = nsub, npath2 = npath, pmin = NEVER, smin = NEVER;
@@ -250,7 +250,7 @@ __device__ __forceinline__ uint32_t member_light(const Dev& d, uint32_t m, uint3
     did |= lt_bit(LT_SYNC);
     d.nextSync[m] = ns + d.sync_t;
     *selp = selc + 1u;
-    send_sync(L, K_SYNC, starget, NONE32, 0, false, dd);
+    send_sync<true>(L, K_SYNC, starget, NONE32, 0, false, dd);
   }
   link_flush(L);
   if (L.syncSeq != w1.w) ms->syncSeq = L.syncSeq;

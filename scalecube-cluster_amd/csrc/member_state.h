@@ -231,9 +231,27 @@ __device__ __forceinline__ void link_flush(ML& L) {
   L.lk_i = NEVER;
 }
 
+// SWIM_EXP & 512 (the wave clock, member.hip), on the light path only (send_sync<true>, member_light.h: the steady
+// state's sends; the general body's sends, k_inbox_apply's among them, compile without the stamps, which cost its
+// split-tick instance 18 more spilled VGPRs): the first lane active here stamps the wall clock into word w of its wave's
+// stamps, once `after` has arrived (the result of the atomic the stamp follows: the wave waits for it here, under the
+// experiment only). Nothing executes with the bit off. The light path runs only in k_member_tick_t<BODY_FULL>, whose
+// grid Dev::wt is sized for.
+template <bool STAMP>
+__device__ __forceinline__ void send_stamp(const Dev& d, uint32_t w, uint32_t after = 0u) {
+  if constexpr (STAMP) {
+    if (!(d.exp & EXP_WAVE_CLOCK)) return;
+    asm volatile("" ::"v"(after));
+    if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)__ballot(1)) - 1))
+      d.wt[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * WT_WORDS + w] = wall_clock64();
+  }
+}
+
 // prepareSyncDataMsg (MembershipProtocolImpl.java:446-454) + transport.send; false if the send failed
 // res: a SYNC_ACK sent in the tick its SYNC was merged (k_ack_resolve may derive its diff from the write logs)
 // dd: xmit_ep's (whether dst is dead at k, when the caller knows; -1: looked up)
+// STAMP: the light path's instance, with the wave clock's stamps (send_stamp)
+template <bool STAMP = false>
 __device__ __forceinline__ bool send_sync(ML& L, uint32_t kind, uint32_t dst, uint32_t ciss, uint32_t ccnt,
                                           bool res = false, int dd = -1) {
   const Dev& d = *L.d;
@@ -245,9 +263,12 @@ __device__ __forceinline__ bool send_sync(ML& L, uint32_t kind, uint32_t dst, ui
     return false;
   }
   uint32_t b = L.k & 1;
-  // one atomic per wave for the lanes sending here together: ~1 300 SYNC / SYNC_ACK sends per tick at C3 on one
-  // counter would otherwise serialise at its L2 channel (~90 per µs)
-  uint32_t i = wave_append(&d.nmsg[b]);
+  // one atomic per wave for the lanes sending here together (~1 300 SYNC / SYNC_ACK sends per tick at C3 on one
+  // counter would otherwise serialise at its L2 channel, ~90 per µs), on the wave's shard of the buffer's slots:
+  // the sending waves of a launch reach this together and would queue on one word (msg_slots.h)
+  send_stamp<STAMP>(d, WT_SLOT0);
+  uint32_t i = msg_take(d, b);
+  send_stamp<STAMP>(d, WT_SLOT1, i);
   if (i >= d.MSGCAP) {
     set_err(d, E_MSGS);
     return true;
@@ -284,6 +305,7 @@ __device__ __forceinline__ bool send_sync(ML& L, uint32_t kind, uint32_t dst, ui
     link_flush(L);
     L.lk_o = atomicExch(&d.m_head[(size_t)b * d.N + dst], i);
     L.lk_i = i;
+    send_stamp<STAMP>(d, WT_LINK, L.lk_o);
   }
   return true;
 }

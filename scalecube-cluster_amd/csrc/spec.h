@@ -193,5 +193,9 @@ enum : uint32_t {
   EXP_WAVE_CLOCK = 512,   // per-wave wall-clock stamps of the latest member kernel (Dev::wt)
   EXP_CYCLES = EXP_CYCLES_SUM | EXP_CYCLES_MAX,
 };
+// Dev::wt, words per wave: 0-3 the kernel's own stamps (entry, after the triage, after the bodies, exit), 4-15 the
+// general body's laps (member.hip Lap), then the light path's send_sync's: just before and just after the wave's latest message-slot
+// reservation, and after the list-link exchange that followed it returned (stamped by the first lane active there)
+constexpr uint32_t WT_WORDS = 20, WT_SLOT0 = 16, WT_SLOT1 = 17, WT_LINK = 18;
 
 }  // namespace swim

@@ -26,7 +26,7 @@ __global__ void __launch_bounds__(256) k_sync_redeliver(Dev d, uint32_t k, uint3
   for (uint32_t e = blockIdx.x; e < d.DSCAP; e += gridDim.x) {
     if (!d.ds_used[e] || d.ds_msg[e].due != k + 1u) continue;
     if (threadIdx.x == 0) {
-      slot[0] = atomicAdd(SHARDED ? &d.xn[4] : &d.nmsg[b], 1u);
+      slot[0] = SHARDED ? atomicAdd(&d.xn[4], 1u) : msg_take(d, b);  // (one lane: its wave's shard, msg_slots.h)
       slot[1] = atomicAdd(&d.arena_used[b], 1u);
       if (slot[0] >= d.MSGCAP) set_err(d, E_MSGS);
       if (slot[1] >= d.ARENA_ROWS) set_err(d, E_ARENA);
@@ -72,8 +72,13 @@ __global__ void __launch_bounds__(256) k_sync_defer(Dev d, uint32_t k, uint32_t 
   // row shards: this tick's list was not committed when the batch halted at it or earlier
   if (spec && (SHARDED ? halted_uncommitted(d.halt, k) : halted_member(d.halt, k))) return;
   __shared__ int32_t slot;
-  const uint32_t b = k & 1, n = min(d.nmsg[b], d.MSGCAP);
-  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+  __shared__ uint32_t mfill[MSG_SHARDS_MAX];
+  const uint32_t b = k & 1;
+  // this tick's messages: the buffer's slots in use (msg_slots.h; a row shard's list is dense, msh == 1)
+  const MsgWalk mw = msg_walk_block(d.ctr_sh, d.msh, d.MSGCAP, b, d.nmsg[b], mfill);
+  for (uint32_t j = blockIdx.x; j < mw.E.total; j += gridDim.x) {
+    const uint32_t i = msg_at(mw, mfill, j);
+    if (i == NEVER) continue;  // (block-uniform)
     const SyncMsg mm = d.msgs[b][i];
     if (!(mm.kind & KF_DEFER)) continue;
     if (threadIdx.x == 0) {

@@ -81,7 +81,7 @@ __device__ __forceinline__ void diff_fetch(const Dev& d, uint32_t b, const uint4
   }
   const uint32_t s0 = c * CH + threadIdx.x * 8;
   // NS is a multiple of 8: a 32-B group is wholly in or out; padding entries are 0 (absent)
-  if (s0 >= d.NS || D.w == DESC_DEFER) {
+  if (s0 >= d.NS || D.w == DESC_DEFER || D.w == DESC_HOLE) {
     x[0] = x[1] = x[2] = x[3] = make_uint4(0, 0, 0, 0);
     return;
   }
@@ -258,33 +258,44 @@ __device__ __forceinline__ uint4 uni(const uint4& v) {
   return make_uint4(__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y),
                     __builtin_amdgcn_readfirstlane(v.z), __builtin_amdgcn_readfirstlane(v.w));
 }
-// list entry j (without a list: message j itself, read from the message buffer)
-__device__ __forceinline__ uint4 diff_entry(const Dev& d, uint32_t b, const uint4* lst, uint32_t j) {
+// list entry j (without a list: the message at position j of the buffer's walk, read from the message buffer; a hole
+// of the walk, msg_slots.h, is a DESC_HOLE entry)
+__device__ __forceinline__ uint4 diff_entry(const Dev& d, uint32_t b, const uint4* lst, uint32_t j, uint32_t mnf,
+                                            uint32_t mR, uint32_t msh, const uint32_t* mfill) {
   if (lst) return lst[j];
-  const SyncMsg& mm = d.msgs[b][j];
-  return make_uint4(j, mm.src, mm.dst, desc_pay(mm));
+  MsgLayout L;
+  MsgEnum E;
+  msg_walk_from(msh, mR, mnf, L, E);
+  const uint32_t i = msg_at(L, E, mfill, j);
+  if (i == NEVER) return make_uint4(0u, 0u, 0u, DESC_HOLE);
+  const SyncMsg& mm = d.msgs[b][i];
+  return make_uint4(i, mm.src, mm.dst, desc_pay(mm));
 }
 
+// mnf, mR, msh (the walk's fast positions, R and log2 of the shards, by value: scalars), mfill: the buffer's walk, read
+// only without a list (n is then its positions)
 template <bool SHARDED>
 __device__ __forceinline__ void stream_wide(const Dev& d, uint32_t b, const uint4* lst, uint32_t n, uint32_t blk,
-                                            uint32_t nblk, uint32_t* scan, uint32_t& base, uint32_t timed) {
+                                            uint32_t nblk, uint32_t* scan, uint32_t& base, uint32_t timed,
+                                            uint32_t mnf, uint32_t mR, uint32_t msh, const uint32_t* mfill) {
   const uint32_t nch = d.NCHUNK, total = n * nch;
   uint4 cur[4], dc = make_uint4(0, 0, 0, 0), dn = dc;
   uint32_t pcur = NEVER;
   bool nw;
   if (blk < total) {
-    dc = uni(diff_entry(d, b, lst, blk / nch));
+    dc = uni(diff_entry(d, b, lst, blk / nch, mnf, mR, msh, mfill));
     diff_fetch<SHARDED>(d, b, dc, blk % nch, cur, pcur, nw, false);
   }
-  if (blk + nblk < total) dn = diff_entry(d, b, lst, (blk + nblk) / nch);
+  if (blk + nblk < total) dn = diff_entry(d, b, lst, (blk + nblk) / nch, mnf, mR, msh, mfill);
   for (uint32_t w = blk; w < total; w += nblk) {
     uint4 nxt[4], dnn = make_uint4(0, 0, 0, 0);
     uint32_t pnxt = NEVER;
     const uint4 du = uni(dn);
     if (w + nblk < total) diff_fetch<SHARDED>(d, b, du, (w + nblk) % nch, nxt, pnxt, nw, false);
-    if (w + 2 * nblk < total) dnn = diff_entry(d, b, lst, (w + 2 * nblk) / nch);
+    if (w + 2 * nblk < total) dnn = diff_entry(d, b, lst, (w + 2 * nblk) / nch, mnf, mR, msh, mfill);
     const uint32_t mi = dc.x, c = w % nch, s0 = c * CH + threadIdx.x * 8;
-    if (!SHARDED && c == 0 && threadIdx.x == 0) {  // priced at 8 B per subject (swim_counters)
+    const bool hole = dc.w == DESC_HOLE;  // (block-uniform: no message here, nothing counted, compared or written)
+    if (!SHARDED && c == 0 && threadIdx.x == 0 && !hole) {  // priced at 8 B per subject (swim_counters)
       atomicAdd(&d.ctr[C_DIFFWIDE_ALL], 1ull);
       if (timed) atomicAdd(&d.ctr[C_DIFFWIDE], 1ull);
     }
@@ -295,7 +306,7 @@ __device__ __forceinline__ void stream_wide(const Dev& d, uint32_t b, const uint
     }
     const uint32_t p[8] = {cur[0].x, cur[0].y, cur[0].z, cur[0].w, cur[1].x, cur[1].y, cur[1].z, cur[1].w};
     const uint32_t r[8] = {cur[2].x, cur[2].y, cur[2].z, cur[2].w, cur[3].x, cur[3].y, cur[3].z, cur[3].w};
-    diff_chunk(d, b, mi, c, s0, p, r, scan, base);
+    if (!hole) diff_chunk(d, b, mi, c, s0, p, r, scan, base);
 #pragma unroll
     for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
     dc = du;
@@ -358,10 +369,20 @@ __global__ void __launch_bounds__(256, DIFF_WAVES) k_sync_diff(const Dev* __rest
     e0 = ((const uint4*)d.dlist)[min(SHARDED ? blockIdx.x / nit : blockIdx.x, cap)];
     e1 = ((const uint4*)d.dlist)[min(SHARDED ? (blockIdx.x + gridDim.x) / nit : blockIdx.x + gridDim.x, cap)];
   }
-  const uint32_t nmsg = d.nmsg[b] < d.MSGCAP ? d.nmsg[b] : d.MSGCAP;
-  const uint32_t nwide = dl ? *(volatile uint32_t*)d.ndlw : nmsg;
-  const uint32_t nnar = dl ? *(volatile uint32_t*)d.ndl : 0u;
+  // without lists: the buffer's walk (msg_slots.h), its positions and among them the messages (the holes left out)
+  __shared__ uint32_t mfill[MSG_SHARDS_MAX];
+  uint32_t mnf = 0, mR = 0, msh = 0;  // the walk's fast positions, R, log2 of the shards
+  uint32_t nwide, nnar = 0;
+  if (dl) {  // (block-uniform)
+    nwide = *(volatile uint32_t*)d.ndlw;
+    nnar = *(volatile uint32_t*)d.ndl;
+  } else {
+    const MsgWalk mw = msg_walk_block(d.ctr_sh, d.msh, d.MSGCAP, b, d.nmsg[b], mfill);
+    mnf = mw.E.nfast, mR = mw.L.R, msh = mw.L.sh, nwide = mw.E.total;
+  }
   if (!dl && blockIdx.x == 0 && threadIdx.x == 0) {
+    uint32_t nmsg = nwide - mnf;
+    for (uint32_t s = 0; msh && s < (1u << msh); ++s) nmsg += mfill[s];
     atomicAdd(&d.ctr[C_DIFFMSG_ALL], (unsigned long long)nmsg);
     if (timed) atomicAdd(&d.ctr[C_DIFFMSG], (unsigned long long)nmsg);
     if (SHARDED) {  // (one GPU: stream_wide counts its messages)
@@ -372,7 +393,7 @@ __global__ void __launch_bounds__(256, DIFF_WAVES) k_sync_diff(const Dev* __rest
   const uint32_t nblk = gridDim.x, ntot = SHARDED ? nnar * ((d.NCHUNK + NPER - 1) / NPER) : nnar;
   if (nnar) stream_narrow<SHARDED>(d, b, (const uint4*)d.dlist, nnar, blockIdx.x, nblk, uni(e0), e1);
   stream_wide<SHARDED>(d, b, dl ? (const uint4*)d.dlist_w : nullptr, nwide, (blockIdx.x + nblk - ntot % nblk) % nblk,
-                       nblk, scan, base, timed);
+                       nblk, scan, base, timed, mnf, mR, msh, mfill);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -412,6 +433,10 @@ struct ResArgs {
   // the pinned live-row payloads (pin_clean); null otherwise (they go to the wide list)
   const uint32_t *m_head, *m_next;
   unsigned long long* pindec;  // the count of those decided (engine.h SH_PINDEC)
+  // the buffer's message-slot shards (msg_slots.h): the counter rows, Dev::msh and the buffer (nmsg above: its overflow
+  // count)
+  unsigned long long* ctr_sh;
+  uint32_t msh, b;
 };
 
 // one GPU: the chunks of item t (chunks NPER t ...) of a narrow payload src -> dst that k_sync_diff must stream, one bit
@@ -559,17 +584,19 @@ __global__ void __launch_bounds__(512) k_ack_resolve(ResArgs d, uint32_t k, uint
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   volatile uint32_t* sv = sv_[wv];  // this wave's lists (volatile: read across lanes)
   volatile uint32_t* sc = sc_[wv];
-  const uint32_t nmsg = min(*d.nmsg, d.MSGCAP);
+  // the buffer's messages: its slots in use, walked densely (msg_slots.h)
+  const MsgDense mw = msg_walk_wave(d.ctr_sh, d.msh, d.MSGCAP, d.b, d.nmsg, lane);
+  const uint32_t npos = mw.total;
   const bool items = d.W == 1;  // the narrow list's form (engine.h NPER)
   const uint32_t nit = (d.NCHUNK + NPER - 1) / NPER;
   // block-uniform loop, one message per wave; the stream list and the counters take one atomic per block (a few
   // hundred waves adding to one address one by one took ~17 us per tick at C3)
-  for (uint32_t base = blockIdx.x * 8; base < nmsg; base += gridDim.x * 8) {
+  for (uint32_t base = blockIdx.x * 8; base < npos; base += gridDim.x * 8) {
     if (threadIdx.x == 0) nstream = nwide = nres = nnarm = nskipm = nchs = nsubj = npind = 0;
     __syncthreads();
-    const uint32_t i = base + wv;
+    const uint32_t i = base + wv < npos ? msg_at_wave(mw, base + wv) : NEVER;  // (NEVER: past the end)
     uint32_t woff = 0, wcnt = 0, src = 0, dst = 0, pw = 0;  // this wave's narrow entries: place in the block's, count
-    if (i < nmsg) {  // wave-uniform
+    if (i != NEVER) {  // wave-uniform
       if (res_wave(d, i, k, lane, sv, sc)) {
         if (lane == 0) atomicAdd(&nres, 1u);
       } else {  // its entries in the narrow list (one GPU, unpinned live row) or its entry in the wide one
@@ -806,7 +833,7 @@ static void launch_ack_resolve(const Dev& d, uint32_t k, hipStream_t st, uint32_
                    d.rowk8 ? 1u : 0u, d.lo, d.W, d.MW, d.mlog, d.base_row, d.rx_mask, d.rx_off, d.xa_recv,
                    (d.ackres & ACKRES_DIRTY) ? d.ms : nullptr, d.W == 1 && d.MW ? 1u : 0u, d.N, d.hflag,
                    lists ? d.m_head + (size_t)b * d.N : nullptr, lists ? d.m_next + (size_t)b * d.MSGCAP : nullptr,
-                   d.ctr_sh + SH_PINDEC};
+                   d.ctr_sh + SH_PINDEC, d.ctr_sh, d.msh, b};
   hipLaunchKernelGGL(k_ack_resolve, dim3(128), dim3(512), 0, st, ra, k, ls, timed ? 1u : 0u);
 }
 
