@@ -90,6 +90,31 @@ int exp_dump_wave_clock(swim_handle* h) {
   }
   fprintf(stderr, "exp512: span %.2f us; mean per wave (us): start %.2f triage %.2f body %.2f cow %.2f\n",
           (tend - t0) / 100.0, sst / nw / 100.0, str / nw / 100.0, sbd / nw / 100.0, scw / nw / 100.0);
+  {  // the front: from the wave's true entry (WT_ENTRY, in front of the halt check) to its first stamp behind the halt
+     // decision, and from there to the stamp after the triage (an entry stamp outside the launch is an earlier one's)
+    std::vector<double> fr, tr;
+    for (size_t i = 0; i < nw; ++i) {
+      const unsigned long long e = wall[WT_WORDS * i + WT_ENTRY], a = w[4 * i], b = w[4 * i + 1] & M;
+      if (e == 0 || e > a || a - e > 100000ull || b < a) continue;
+      fr.push_back((a - e) / 100.0), tr.push_back((b - a) / 100.0);
+    }
+    std::sort(fr.begin(), fr.end());
+    std::sort(tr.begin(), tr.end());
+    if (!fr.empty())
+      fprintf(stderr, "exp512: front, waves %zu: entry to first stamp us q1 %.2f med %.2f q3 %.2f max %.2f; first stamp to "
+              "post-triage us q1 %.2f med %.2f q3 %.2f max %.2f\n", fr.size(), fr[fr.size() / 4], fr[fr.size() / 2],
+              fr[3 * fr.size() / 4], fr.back(), tr[tr.size() / 4], tr[tr.size() / 2], tr[3 * tr.size() / 4], tr.back());
+    // the body (post-triage to body end) of the class-3 waves that sent nothing in this launch: pings only
+    std::vector<double> pb;
+    for (size_t i = 0; i < nw; ++i) {
+      const unsigned long long a = wall[WT_WORDS * i + WT_SLOT0], lo = w[4 * i + 1] & M, hi = w[4 * i + 2];
+      if ((w[4 * i + 1] >> 56) == 8ull && (a < lo || a > hi) && hi >= lo) pb.push_back((hi - lo) / 100.0);
+    }
+    std::sort(pb.begin(), pb.end());
+    if (!pb.empty())
+      fprintf(stderr, "exp512: class 3 waves without a send %zu: body us q1 %.2f med %.2f q3 %.2f max %.2f\n", pb.size(),
+              pb[pb.size() / 4], pb[pb.size() / 2], pb[3 * pb.size() / 4], pb.back());
+  }
   {  // send_sync's stamps (WT_SLOT0, WT_SLOT1, WT_LINK) of the waves that sent in this launch (a stamp outside the
      // wave's bodies is an earlier launch's): the slot reservation's round trip and the time from its return to the
      // list-link exchange's, per class; then the reservation's round trip against the order the waves issued it in

@@ -232,14 +232,16 @@ void launch_init(const Dev& d, void* stream) {
 
 void launch_member(const Dev& d, uint32_t k, void* stream, const TickEvents* prof, bool spec, bool split, uint32_t lf) {
   hipStream_t st = (hipStream_t)stream;
+  const MemberFront f = member_front(d);  // the front's addresses as an argument (member_kernels.h)
   if (prof && prof->all) hipEventRecord((hipEvent_t)prof->ev[2], st);
   if (split) {  // a gossip plane ran last tick: members with many routed receipts run P4 a wave each (k_inbox_apply)
-    hipLaunchKernelGGL(k_member_tick_t<BODY_SPLIT>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k, 0u);  // (the second launch closes the tick)
+    // (the second launch closes the tick)
+    hipLaunchKernelGGL(k_member_tick_t<BODY_SPLIT>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k, 0u, f);
     hipLaunchKernelGGL(k_inbox_apply, dim3(2048), dim3(256), 0, st, d.self, k);
-    hipLaunchKernelGGL(k_member_tick_t<BODY_RESUME>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k, MT_END);  // + tick_flag
+    hipLaunchKernelGGL(k_member_tick_t<BODY_RESUME>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k, MT_END, f);  // + tick_flag
   } else {
     hipLaunchKernelGGL(k_member_tick_t<BODY_FULL>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k,
-                       MT_END | (spec ? MT_SPEC | lf : 0u));  // + tick_flag, or (speculative) tick_reset
+                       MT_END | (spec ? MT_SPEC | lf : 0u), f);  // + tick_flag, or (speculative) tick_reset
   }
   if (d.dly_on) {
     launch_sync_redeliver(d, k, st, spec);
@@ -263,7 +265,8 @@ void launch_tick_a(const Dev& d, uint32_t k, void* stream, const TickEvents* pro
   const uint32_t sp = spec ? 1u : 0u;
   launch_diff(d, k, stream, prof, spec ? LS_SPEC : 0u);
   if (prof && prof->all) hipEventRecord((hipEvent_t)prof->ev[2], st);
-  hipLaunchKernelGGL(k_member_tick_t<BODY_FULL>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k, spec ? MT_SPEC : 0u);
+  hipLaunchKernelGGL(k_member_tick_t<BODY_FULL>, dim3(cdiv(d.NL, 256)), dim3(256), 0, st, d.self, k, spec ? MT_SPEC : 0u,
+                     member_front(d));
   if (prof && prof->all) hipEventRecord((hipEvent_t)prof->ev[3], st);
   if (d.dly_on) launch_sync_redeliver(d, k, st, spec);
   hipLaunchKernelGGL(k_pack_all, dim3(16, d.W), dim3(256), 0, st, d, b, sp);  // route + exchange-A regions

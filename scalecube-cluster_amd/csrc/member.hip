@@ -25,15 +25,36 @@ namespace swim {
 // light (member_light.h light_mode; 0: the classes above): a member whose causes the light path knows (an inbound SYNC
 // list, a request event, a ping, the periodic SYNC, an empty gossip round) gets class 1 (a list), 3 (a
 // ping or a SYNC due) or 2, everything that needs the general body class 0; head: its inbound list head, for that path
+// tw: the member's triage words (triage_load)
+struct TriageWords {
+  uint32_t mh, rc, pi, ne, tm, np, ns, inf, ng, held, dt, st, nd;
+};
+// every word is loaded up front (no short-circuit chain of dependent loads); the SoA loads coalesce per wave
+// (BODY_SPLIT: through Dev, as before the split from member_triage)
+__device__ __forceinline__ TriageWords triage_load(const Dev& d, uint32_t m, uint32_t k) {
+  return TriageWords{d.m_head[(size_t)((k - 1) & 1) * d.N + m], d.rc_cnt[m], d.pending_inc[m], d.next_evt[m], d.timerMin[m],
+                     d.nextPing[m], d.nextSync[m], d.initFlags[m], d.nextGossip[m], d.held[m], d.dead_tick[m],
+                     d.start_tick[m], d.rc_ndrop[m]};
+}
+// the same from the launch's argument (member_kernels.h MemberFront): no load of a pointer in front of the loads
+__device__ __forceinline__ TriageWords triage_load(const MemberFront& f, uint32_t m, uint32_t k) {
+  return TriageWords{f.m_head[(size_t)((k - 1) & 1) * f.N + m], f.rc_cnt[m], f.pending_inc[m], f.next_evt[m], f.timerMin[m],
+                     f.nextPing[m], f.nextSync[m], f.initFlags[m], f.nextGossip[m], f.held[m], f.dead_tick[m],
+                     f.start_tick[m], f.rc_ndrop[m]};
+}
+// the triage's loads and the halt words' (spec.h halt_load) are issued here and have arrived behind this point: the
+// launch's halt decision and the triage then wait once, for both
+__device__ __forceinline__ void triage_arrived(const TriageWords& t, const HaltWords& h) {
+  asm volatile("" ::"v"(t.mh), "v"(t.rc), "v"(t.pi), "v"(t.ne), "v"(t.tm), "v"(t.np), "v"(t.ns), "v"(t.inf), "v"(t.ng),
+               "v"(t.held), "v"(t.dt), "v"(t.st), "v"(t.nd), "v"(h.hg), "v"(h.hd), "v"(h.listed), "v"(h.hw));
+}
 __device__ __forceinline__ bool member_triage(const Dev& d, uint32_t m, uint32_t k, uint32_t& cls, uint32_t& drops,
-                                              uint32_t& evs, bool nolist, uint64_t& lfc, uint32_t light, uint32_t& head) {
+                                              uint32_t& evs, bool nolist, uint64_t& lfc, uint32_t light, uint32_t& head,
+                                              const TriageWords& tw) {
   // A dead member does nothing itself, but the remote hops of its in-flight requests still run at the live
   // responders (their sends fail against the dead issuer), so those hops are still evaluated for the counters.
-  // every word is loaded up front (no short-circuit chain of dependent loads); the SoA loads coalesce per wave
-  const uint32_t mh = d.m_head[(size_t)((k - 1) & 1) * d.N + m], rc = d.rc_cnt[m], pi = d.pending_inc[m],
-                 ne = d.next_evt[m], tm = d.timerMin[m], np = d.nextPing[m], ns = d.nextSync[m], inf = d.initFlags[m],
-                 ng = d.nextGossip[m], held = d.held[m], dt = d.dead_tick[m], st = d.start_tick[m],
-                 nd = d.rc_ndrop[m];
+  const uint32_t mh = tw.mh, rc = tw.rc, pi = tw.pi, ne = tw.ne, tm = tw.tm, np = tw.np, ns = tw.ns, inf = tw.inf, ng = tw.ng,
+                 held = tw.held, dt = tw.dt, st = tw.st, nd = tw.nd;
   const bool dead = k >= dt;
   cls = 0;
   drops = 0;
@@ -713,11 +734,31 @@ __device__ __forceinline__ void member_tick_body(const Dev& d, uint32_t m, uint3
 // (MODE: BODY_FULL, or the two launches around k_inbox_apply, BODY_SPLIT and BODY_RESUME: three kernels, each with its
 // own register allocation, so the steady-state one keeps the code it had before the split)
 template <uint32_t MODE>
-__global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict__ dp, uint32_t k, uint32_t flag) {
+__global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict__ dp, uint32_t k, uint32_t flag,
+                                                          const MemberFront f) {
+  // SWIM_EXP & 512: the wave's clock at its true entry, in front of the halt check and every load (stored as wt[WT_ENTRY]
+  // once the launch is known to run: a halted launch stores nothing). Read only with the bit set, which the launch's
+  // argument carries (f.exp: no load in front of it), and only by BODY_FULL, the instance the experiment traces.
+  const unsigned long long t_entry = MODE == BODY_FULL && (f.exp & EXP_WAVE_CLOCK) ? wall_clock64() : 0ull;
   const Dev& d = *dp;  // global, not kernarg: taking its address must not copy ~1 KB into per-lane scratch
+  const uint32_t m = (MODE == BODY_FULL ? f.lo : d.lo) + blockIdx.x * blockDim.x + threadIdx.x;
   // a speculative batch halted at an earlier tick (this tick's own halt is raised while it runs), or by a diff-halt:
   // returning before tick_reset keeps the lists and the pool as the lister left them (spec.h)
-  if (mt_spec(flag) && halted_member(d.halt, k, mt_lf(flag))) return;
+  // BODY_FULL: the halt words are loaded together with the triage's words, and the launch decides when both have
+  // arrived: one wait where the halt check took its own in front of everything. Until the decision nothing is stored
+  // and no atomic is issued, so a halted launch leaves no trace. (A lane past f.hi loads the last member's words: no
+  // branch around the loads; member_triage is not called for it. f.hi >= 1: a launch has a block only if its range
+  // [lo, hi) holds a member, so f.hi - 1 is the last member and the clamp keeps every lane inside the arrays.)
+  TriageWords tw;
+  if constexpr (MODE == BODY_FULL) {
+    // Every address comes from the launch's argument f (member_kernels.h): no scalar load through dp lies in front.
+    const HaltWords hw = halt_load(f.halt);  // (every launch: a branch around the load would wait for it at its end)
+    tw = triage_load(f, min(m, f.hi - 1u), k);
+    triage_arrived(tw, hw);
+    if (mt_spec(flag) && halted_member(hw, k, mt_lf(flag))) return;
+  } else {
+    if (mt_spec(flag) && halted_member(d.halt, k, mt_lf(flag))) return;
+  }
   // a speculative launch resets the next tick's counters at its start (nothing in this kernel uses them), so no block
   // waits for the last one at its end: the halt that tick_flag would raise is raised by the member taking a slot
   // (a split tick's launches are never speculative: kernels.hip launch_member)
@@ -726,7 +767,10 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   // SWIM_EXP & 512 (timing experiment): wall clock of each wave at entry, after triage, after its bodies, at exit
   const bool wtime = (d.exp & EXP_WAVE_CLOCK) != 0;
   unsigned long long* wt = wtime ? d.wt + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * WT_WORDS : nullptr;
-  if (wtime && (threadIdx.x & 63) == 0) wt[0] = wall_clock64();
+  if (wtime && (threadIdx.x & 63) == 0) {
+    wt[0] = wall_clock64();
+    if (MODE == BODY_FULL) wt[WT_ENTRY] = t_entry;
+  }
   __shared__ uint32_t wc[4][4];  // [wave][class] busy members
   __shared__ uint32_t list[256];
   __shared__ uint4 cw[CWMAX];  // deferred copy-on-write snapshots of this block's members (cow)
@@ -734,7 +778,6 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   if (threadIdx.x == 0) cw_n = 0;
   if (threadIdx.x < CWMAX) cw[threadIdx.x].x = NEVER;  // no member until written (cow scans by member)
   constexpr bool resume = MODE == BODY_RESUME;  // the parked members' P5 and P6 (one lane each, from the list)
-  const uint32_t m = d.lo + blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t cls = 0, drops = 0, evs = 0;
   // no lister ran for this tick: each lane's share of the lister's counts (lf_count), from the triage and from P1 (in
   // LDS: a register would be held across the whole body)
@@ -749,7 +792,9 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   __shared__ uint32_t fb_n;
   if (MODE == BODY_FULL && threadIdx.x == 0) fb_n = 0;
   uint32_t mhead = NEVER;
-  const bool busy = !resume && m < d.hi && member_triage(d, m, k, cls, drops, evs, nolist, lft, light, mhead);
+  const bool busy = !resume && m < d.hi &&
+                    member_triage(d, m, k, cls, drops, evs, nolist, lft, light, mhead,
+                                  MODE == BODY_FULL ? tw : triage_load(d, m, k));
   if (nolist) lfs[threadIdx.x] = lft;
   {  // the triage's record compares and folded RUMOR events, one atomic each per wave
     const uint32_t v = wave_sum(drops), e = wave_sum(evs);
@@ -880,8 +925,8 @@ __global__ void __launch_bounds__(256, 2) k_member_tick_t(const Dev* __restrict_
   tick_flag(d, k);
 }
 
-template __global__ void k_member_tick_t<BODY_FULL>(const Dev* __restrict__, uint32_t, uint32_t);
-template __global__ void k_member_tick_t<BODY_SPLIT>(const Dev* __restrict__, uint32_t, uint32_t);
-template __global__ void k_member_tick_t<BODY_RESUME>(const Dev* __restrict__, uint32_t, uint32_t);
+template __global__ void k_member_tick_t<BODY_FULL>(const Dev* __restrict__, uint32_t, uint32_t, const MemberFront);
+template __global__ void k_member_tick_t<BODY_SPLIT>(const Dev* __restrict__, uint32_t, uint32_t, const MemberFront);
+template __global__ void k_member_tick_t<BODY_RESUME>(const Dev* __restrict__, uint32_t, uint32_t, const MemberFront);
 
 }  // namespace swim

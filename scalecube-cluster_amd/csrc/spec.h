@@ -3,8 +3,8 @@
 //
 // A speculative batch is a run of ticks queued with no host wait (one GPU: spec_batch; row shards over RCCL:
 // shard_spec_batch). Device words, Dev::halt, decide which of the queued launches still do anything. A launch of
-// tick k reads them at its start (volatile loads; hg = halt[HALT_GOSSIP], hd = halt[HALT_DIFF], hw = halt[HALT_WROTE])
-// and returns at once by the rule of its kernel; nothing waits on the device, and the host reads the words back after
+// tick k reads them at its start (all at once, system scope: halt_load; hg = halt[HALT_GOSSIP], hd = halt[HALT_DIFF],
+// hw = halt[HALT_WROTE]) and returns at once by the rule of its kernel; nothing waits on the device, and the host reads the words back after
 // the batch. hw takes part only in the launches of a lister-free batch (LS_LF, MT_LF; below): the other one-GPU
 // batches write it (the host looks at it before it enters the mode) but never read it on the device.
 //
@@ -84,34 +84,57 @@ enum HaltWord : uint32_t {
   HALT_WORDS = 5  // adjacent: one copy reads them back
 };
 
-__device__ __forceinline__ bool halted(const uint32_t* halt) { return *(volatile const uint32_t*)halt != 0u; }
-// lf: a launch of a lister-free batch (LS_LF, MT_LF): a member kernel of an earlier tick wrote
-__device__ __forceinline__ bool halted_wrote(const uint32_t* halt, uint32_t k, bool lf) {
-  if (!lf) return false;
-  const uint32_t hw = *(volatile const uint32_t*)(halt + HALT_WROTE);
-  return hw != 0u && hw <= k;
-}
-__device__ __forceinline__ bool halted_diff(const uint32_t* halt, bool lf) {
-  return (*(volatile const uint32_t*)(halt + HALT_GOSSIP) | *(volatile const uint32_t*)(halt + HALT_DIFF)) != 0u ||
-         (lf && *(volatile const uint32_t*)(halt + HALT_WROTE) != 0u);
-}
-__device__ __forceinline__ bool halted_lister(const uint32_t* halt, uint32_t k, bool lf) {
-  const uint32_t hg = *(volatile const uint32_t*)(halt + HALT_GOSSIP), hd = *(volatile const uint32_t*)(halt + HALT_DIFF);
-  return hg || (hd && hd != k + 1u) || halted_wrote(halt, k, lf);
-}
-__device__ __forceinline__ bool halted_before(const uint32_t* halt, uint32_t k) {
-  const uint32_t hg = *(volatile const uint32_t*)(halt + HALT_GOSSIP);
-  return hg != 0u && hg - 1u < k;
-}
-__device__ __forceinline__ bool halted_uncommitted(const uint32_t* halt, uint32_t k) { return halted_before(halt, k + 1u); }
-__device__ __forceinline__ bool halted_member(const uint32_t* halt, uint32_t k, bool lf = false) {
-  return halted_before(halt, k) || *(volatile const uint32_t*)(halt + HALT_DIFF) != 0u || halted_wrote(halt, k, lf);
+// The words a launch decides on, HALT_GOSSIP .. HALT_WROTE, read once, the four adjacent words as one 16-byte line
+// segment (Dev::halt is 16-byte aligned: word SH_HALT of the counter rows' allocation, or an allocation of its own), so
+// no predicate waits for one word after the other. Every predicate of the table above decides on a HaltWords; the
+// overloads that take the pointer load and decide.
+// The loads are system-scope like the volatile loads they replace (the same cache-bypass bits), but relaxed atomics, two
+// of 8 bytes issued back to back: the compiler completes every volatile load with a full vector-memory wait directly
+// behind it (which is what made three words three serial round trips), and it has no 16-byte atomic. A caller may so
+// issue further loads behind these and wait once for all of them (member.hip).
+struct HaltWords {
+  uint32_t hg, hd, listed, hw;
+};
+static_assert(HALT_GOSSIP == 0 && HALT_DIFF == 1 && HALT_LISTED == 2 && HALT_WROTE == 3, "HaltWords is the first four halt words");
+__device__ __forceinline__ HaltWords halt_load(const uint32_t* halt) {
+  // (global loads: the words are device memory, and a FLAT load would count on the scalar loads' wait counter too)
+  typedef const __attribute__((address_space(1))) unsigned long long* G;
+  const unsigned long long a = __hip_atomic_load((G)halt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM),
+                           b = __hip_atomic_load((G)halt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  return HaltWords{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
 }
 
+__device__ __forceinline__ bool halted(const HaltWords& h) { return h.hg != 0u; }
+// lf: a launch of a lister-free batch (LS_LF, MT_LF): a member kernel of an earlier tick wrote
+__device__ __forceinline__ bool halted_wrote(const HaltWords& h, uint32_t k, bool lf) { return lf && h.hw != 0u && h.hw <= k; }
+__device__ __forceinline__ bool halted_diff(const HaltWords& h, bool lf) { return (h.hg | h.hd) != 0u || (lf && h.hw != 0u); }
+__device__ __forceinline__ bool halted_lister(const HaltWords& h, uint32_t k, bool lf) {
+  return h.hg || (h.hd && h.hd != k + 1u) || halted_wrote(h, k, lf);
+}
+__device__ __forceinline__ bool halted_before(const HaltWords& h, uint32_t k) { return h.hg != 0u && h.hg - 1u < k; }
+__device__ __forceinline__ bool halted_uncommitted(const HaltWords& h, uint32_t k) { return halted_before(h, k + 1u); }
+__device__ __forceinline__ bool halted_member(const HaltWords& h, uint32_t k, bool lf = false) {
+  return halted_before(h, k) || h.hd != 0u || halted_wrote(h, k, lf);
+}
 // a recorded watch sample of tick t >= 1, queued behind member(t - 1): the state at rest at tick t does not exist (yet)
+__device__ __forceinline__ bool halted_sample(const HaltWords& h, uint32_t t, bool lf) {
+  return halted_uncommitted(h, t - 1u) || h.hd != 0u || halted_wrote(h, t - 1u, lf);
+}
+
+__device__ __forceinline__ bool halted(const uint32_t* halt) { return halted(halt_load(halt)); }
+__device__ __forceinline__ bool halted_diff(const uint32_t* halt, bool lf) { return halted_diff(halt_load(halt), lf); }
+__device__ __forceinline__ bool halted_lister(const uint32_t* halt, uint32_t k, bool lf) {
+  return halted_lister(halt_load(halt), k, lf);
+}
+__device__ __forceinline__ bool halted_before(const uint32_t* halt, uint32_t k) { return halted_before(halt_load(halt), k); }
+__device__ __forceinline__ bool halted_uncommitted(const uint32_t* halt, uint32_t k) {
+  return halted_uncommitted(halt_load(halt), k);
+}
+__device__ __forceinline__ bool halted_member(const uint32_t* halt, uint32_t k, bool lf = false) {
+  return halted_member(halt_load(halt), k, lf);
+}
 __device__ __forceinline__ bool halted_sample(const uint32_t* halt, uint32_t t, bool lf) {
-  return halted_uncommitted(halt, t - 1u) || *(volatile const uint32_t*)(halt + HALT_DIFF) != 0u ||
-         halted_wrote(halt, t - 1u, lf);
+  return halted_sample(halt_load(halt), t, lf);
 }
 
 __device__ __forceinline__ void raise_gossip_halt(uint32_t* halt, uint32_t k) {
@@ -196,6 +219,8 @@ enum : uint32_t {
 // Dev::wt, words per wave: 0-3 the kernel's own stamps (entry, after the triage, after the bodies, exit), 4-15 the
 // general body's laps (member.hip Lap), then the light path's send_sync's: just before and just after the wave's latest message-slot
 // reservation, and after the list-link exchange that followed it returned (stamped by the first lane active there)
-constexpr uint32_t WT_WORDS = 20, WT_SLOT0 = 16, WT_SLOT1 = 17, WT_LINK = 18;
+// Word 19: the wave's clock at the kernel's true entry, in front of the halt check and every load (word 0 is stamped behind
+// the halt decision).
+constexpr uint32_t WT_WORDS = 20, WT_SLOT0 = 16, WT_SLOT1 = 17, WT_LINK = 18, WT_ENTRY = 19;
 
 }  // namespace swim
